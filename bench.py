@@ -16,13 +16,20 @@ still, uv_checker + cubemap array) unless --textures standin. The camera is
 the app's default one, or the app's H-key flyby (--camera flyby: a new
 hyperbolicTrajectory camera every frame).
 
-Also reported (rank 0): the integrate kernel's roofline - executed FP32 FLOP
+A plain run does only that: it sets up, warms up, times the K frames, writes
+the last timed frame with --dump-outputs DIR (DIR/frame.npy, float32) and
+prints the line. Everything below runs only with --full, and the line's
+`roofline`, `cpu_baseline`, `parity`, `config.single_frame`,
+`config.frame_latency_ms` and `config.last_camera_max_over_mean` are null
+without it.
+
+With --full also reported (rank 0): the integrate kernel's roofline - executed FP32 FLOP
 per launch from rocprofv3 counters (profiles/pmc_latest.json, matched to this
 kernel source and config) over the same timed run's frame time - and the
 reference's CPU press-R geodesic loop swept over a sample of the frame's
 pixels on this host (cpu_baseline; oracle restatement, "port").
 
-  python bench.py [--gpus N --steps K --warmup W]   (N > 1: spawns N ranks, launch_contract)
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   (N > 1: spawns N ranks, launch_contract)
   torchrun --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -196,6 +203,15 @@ def parse():
     ap.add_argument("--dump-frames", default="",
                     help="directory: rank 0 saves every timed frame as assembled (frame_<f>.npy), for the "
                          "multi-rank parity test; copies are taken after the timed region")
+    ap.add_argument("--dump-outputs", default="",
+                    help="directory: rank 0 saves the last timed frame as assembled (what the timed path's caller "
+                         "receives) as frame.npy, float32 [rows, width, 4]; a frame over 64 MB as a fixed, seeded "
+                         "sample of its rows (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the step map and roofline, the parity check "
+                         "against the frame-hash fixture, frame latency, single-frame launches, the reference "
+                         "loop, the critical path and the CPU baseline (each still has its own on/off option); "
+                         "without it the run only sets up, warms up, times --steps frames and prints the line")
     ap.add_argument("--traffic-json", default="",
                     help="HBM traffic record (default profiles/traffic_latest[_<variant>].json)")
     ap.add_argument("--pmc-json", default="",
@@ -514,9 +530,11 @@ def main():
         for c in ctxs:
             c[3].synchronize()
 
-    # executed steps of this rank's rows (untimed; the debug variant of the kernel)
-    _, _, steps_full = r.render_debug(cams[0], params, W, H)
-    torch.cuda.synchronize(dev)
+    # executed steps of this rank's rows (--full; untimed; the debug variant of the kernel)
+    steps_full = None
+    if args.full:
+        _, _, steps_full = r.render_debug(cams[0], params, W, H)
+        torch.cuda.synchronize(dev)
     balance = None
     balance_used = args.balance if args.balance != "auto" else ("cost" if args.camera == "static" else "cyclic")
     if distributed and balance_used == "cost":
@@ -545,13 +563,14 @@ def main():
             rp["stream"] = torch.cuda.Stream(dev)
     else:
         rows_mine = D.rows_of(rank, world, H, BLOCK_ROWS)
-    sigma_steps_frame = int(steps_full.sum().item())
-    sigma_steps_mine = int(steps_full[rows_mine].sum().item())
-    # candidate critical bands: the 16-row bands of workgroup tiles holding the
-    # frame's longest rays (the slowest of them is timed below)
-    band_max = steps_full.max(dim=1).values[: H // 16 * 16].view(-1, 16).max(dim=1).values
-    band_rows = [int(b) * 16 for b in band_max.argsort(descending=True)[:CRITICAL_CANDIDATES].tolist()] or [0]
-    del steps_full, band_max
+    if args.full:
+        sigma_steps_frame = int(steps_full.sum().item())
+        sigma_steps_mine = int(steps_full[rows_mine].sum().item())
+        # candidate critical bands: the 16-row bands of workgroup tiles holding the
+        # frame's longest rays (the slowest of them is timed below)
+        band_max = steps_full.max(dim=1).values[: H // 16 * 16].view(-1, 16).max(dim=1).values
+        band_rows = [int(b) * 16 for b in band_max.argsort(descending=True)[:CRITICAL_CANDIDATES].tolist()] or [0]
+        del steps_full, band_max
 
     run_frames(0, warm)
     sync_all()
@@ -581,7 +600,10 @@ def main():
     parity = None
     if rank == 0 and last[0] is not None:
         first, batch = last[0]
-        parity = frame_parity(args, W, H, N, quality, use_assets, batch[-1], first + batch.shape[0] - 1)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, batch[-1], H)
+        if args.full:
+            parity = frame_parity(args, W, H, N, quality, use_assets, batch[-1], first + batch.shape[0] - 1)
     ktimes = np.concatenate([c[0].kernel_times(per_ctx) for c in ctxs], axis=0)
     # frames of each row of ktimes: launch j of the window ran on context j % F
     # (run_frames), and each context lists its own launches in order
@@ -598,27 +620,29 @@ def main():
 
     # frame latency (untimed for `value`): one launch of B frames alone on
     # context 0; every frame of it is done when the launch is
-    lat_launches = 5
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record(stream)
-    for _ in range(lat_launches):
-        render(r, warm, min(B, args.steps), tile, stream)
-    ev1.record(stream)
-    torch.cuda.synchronize(dev)
-    latency_ms = ev0.elapsed_time(ev1) / lat_launches
+    latency_ms = 0.0  # --full only
+    if args.full:
+        lat_launches = 5
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record(stream)
+        for _ in range(lat_launches):
+            render(r, warm, min(B, args.steps), tile, stream)
+        ev1.record(stream)
+        torch.cuda.synchronize(dev)
+        latency_ms = ev0.elapsed_time(ev1) / lat_launches
 
     # Single-frame launches (untimed for `value`; the reference draws one frame
     # per loop iteration, src/main.cpp:318-319, camera re-uploaded each time,
     # :429): one frame alone (B = 1, F = 1: the interactive latency) and
     # single-frame launches with 4 in flight (B = 1, F = 4).
     single = None
-    if world == 1 and args.single_frame == "on":
+    if args.full and world == 1 and args.single_frame == "on":
         single = single_frames(new_renderer, ctxs, cams, params, W, H, dev, args.single_split, render, warm,
                                restore=split)
 
     # the reference's loop: one un-culled frame against one culled frame, alone
     speedup_ref = None
-    if args.reference_loop == "on" and not args.no_cull and rank == 0:
+    if args.full and args.reference_loop == "on" and not args.no_cull and rank == 0:
         def alone_integrate_ms(cull):
             r.set_culling(cull)
             r.set_timing(2)
@@ -640,7 +664,7 @@ def main():
         if rank == 0:
             balance["reprice_choices"] = rp["choices"]
     last_camera = None
-    if distributed and args.camera == "flyby" and rank == 0:
+    if args.full and distributed and args.camera == "flyby" and rank == 0:
         # how even the lists in use (and the frame-0 lists, cyclic rows) are on
         # the last timed camera, by its full-resolution cost map (untimed)
         cost_last = D.block_costs(r.wave_costs(cams[warm + args.steps - 1], params, W, H, stream=stream).cpu())
@@ -677,7 +701,7 @@ def main():
     # so the frame's launch-order state stays untouched. Its time is the
     # slowest waves' latency without contention.
     critical = None
-    if rank == 0 and world == 1 and args.critical_path == "on":
+    if args.full and rank == 0 and world == 1 and args.critical_path == "on":
         rb = new_renderer()
 
         def band_time(band, reps):
@@ -703,11 +727,13 @@ def main():
                     "frac_of_frame_latency": round(band_ms / latency_ms, 3)}
 
     if rank == 0:
-        roofline = make_roofline(args, W, H, N, world, F, B, ms_per_step, ktimes, launch_frames,
-                                 latency_ms, sigma_steps_frame, sigma_steps_mine, len(rows_mine), critical,
-                                 speedup_ref)
+        roofline = None
+        if args.full:
+            roofline = make_roofline(args, W, H, N, world, F, B, ms_per_step, ktimes, launch_frames,
+                                     latency_ms, sigma_steps_frame, sigma_steps_mine, len(rows_mine), critical,
+                                     speedup_ref)
         cpu = None
-        if args.cpu_baseline == "auto" and world == 1:
+        if args.full and args.cpu_baseline == "auto" and world == 1:
             cpu = cpu_baseline(cams[0], W, H, N, args.cpu_sample_rows)
         tex_desc = (f"the reference's assets/textures ({quality} skybox, uv_checker, cubemap; decoded to stb_image's bytes)"
                     if use_assets else f"procedural stand-in textures ({quality} skybox)")
@@ -719,6 +745,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "strong",
@@ -757,7 +784,7 @@ def main():
                 "launch_sizes": [min(B, args.steps - f) for f in range(0, args.steps, B)],
                 "split_tiles": args.split,
                 "gpu_max_hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
-                "frame_latency_ms": round(latency_ms, 4),
+                "frame_latency_ms": round(latency_ms, 4) if args.full else None,
                 "single_frame": single,
                 "culling": not args.no_cull,
                 "world_size": world,
@@ -873,6 +900,38 @@ def single_frames(new_renderer, ctxs, cams, params, W, H, dev, split_arg, render
                      "mpix_s": round(W * H / per / 1e3, 3), "frames": frames, "stat": "wall clock",
                      "split_tiles": "0"},
     }
+
+
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: everything written, .npy headers included
+DUMP_SEED = 0
+
+
+def dump_rows(height, row_bytes, max_bytes=DUMP_MAX_BYTES, seed=DUMP_SEED):
+    """Rows of a frame --dump-outputs writes: every row when the float32 frame
+    fits max_bytes, else as many as fit, drawn without replacement by a
+    generator seeded with `seed` and sorted (the same rows every run)."""
+    import numpy as np
+
+    fit = max(1, (max_bytes - 4096) // row_bytes)  # 4096: room for the .npy header
+    if fit >= height:
+        return np.arange(height)
+    return np.sort(np.random.default_rng(seed).choice(height, fit, replace=False))
+
+
+def dump_outputs(directory, frame, H):
+    """--dump-outputs: the last timed frame as its caller receives it (RGBA8,
+    [H, W, 4], assembled on rank 0) as <directory>/frame.npy in float32
+    (0..255, exact), rows dump_rows(H, ...) of it. The inputs are the same
+    every run of the same command line (scene, camera path and textures are
+    fixed), so two builds' files compare value for value."""
+    import numpy as np
+
+    fr = frame.cpu().numpy() if hasattr(frame, "cpu") else np.asarray(frame)
+    fr = fr[:H]
+    rows = dump_rows(H, fr.shape[1] * fr.shape[2] * 4)
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "frame.npy", np.ascontiguousarray(fr[rows]).astype(np.float32))
 
 
 FRAME_HASHES = ROOT / "tests" / "golden" / "frame_hashes.npz"

@@ -1,11 +1,13 @@
 """bench.py's command line (driver contract) and its workloads against
-BASELINE.json's configs; no GPU needed."""
+BASELINE.json's configs; no GPU needed but for the one plain run marked gpu."""
 import argparse
 import json
 import re
 import subprocess
 import sys
 from pathlib import Path
+
+import pytest
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
@@ -34,6 +36,67 @@ def test_defaults_are_the_headline_on_one_gpu():
 def test_driver_flags_parse():
     a = _parse(["--gpus", "8", "--steps", "5", "--warmup", "2"])
     assert (a.gpus, a.steps, a.warmup) == (8, 5, 2)
+
+
+def test_full_and_dump_outputs_are_off_by_default():
+    a = _parse([])
+    assert a.full is False and a.dump_outputs == ""
+    a = _parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_within_the_cap(tmp_path):
+    """--dump-outputs: the frame's rows as float32 (exact for RGBA8), every
+    row when they fit 64 MB, else a seeded row sample that is the same every
+    run; padding rows past the frame's height are dropped."""
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(1)
+    fr = rng.integers(0, 256, size=(24, 20, 4), dtype=np.uint8)  # 21 rows + 3 of tile padding
+    bench.dump_outputs(tmp_path / "d", fr, 21)
+    assert [p.name for p in (tmp_path / "d").iterdir()] == ["frame.npy"]
+    got = np.load(tmp_path / "d" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (21, 20, 4) and np.array_equal(got, fr[:21])
+    # the headline frame fits whole, the 4k and 8k frames do not
+    assert np.array_equal(bench.dump_rows(1080, 1920 * 4 * 4), np.arange(1080))
+    for w, h in ((3840, 2160), (7680, 4320)):
+        rows = bench.dump_rows(h, w * 4 * 4)
+        assert 0 < len(rows) < h and len(set(rows.tolist())) == len(rows) and np.all(np.diff(rows) > 0)
+        assert 0 <= rows[0] and rows[-1] < h
+        assert 128 + len(rows) * w * 4 * 4 <= 64_000_000 < 128 + (len(rows) + 1) * w * 4 * 4 + 4096
+        assert np.array_equal(rows, bench.dump_rows(h, w * 4 * 4))
+    small = bench.dump_rows(21, 320, max_bytes=4096 + 5 * 320)
+    assert len(small) == 5 and not np.array_equal(small, np.arange(5))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_frame(tmp_path):
+    """A plain run (no --full) prints the headline fields with everything
+    else null, times exactly --steps frames, and --dump-outputs holds the
+    last of them: the same frame --dump-frames saves."""
+    import numpy as np
+
+    r = _bench(["--gpus", "1", "--width", "320", "--height", "180", "--max-steps", "800", "--steps", "5",
+                "--warmup", "1", "--camera", "flyby", "--dump-outputs", str(tmp_path / "o"),
+                "--dump-frames", str(tmp_path / "f")], timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["full"] is False and d["ms_per_step"] > 0 and d["unit"] == "Mpixels/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 320 * 180 / d["ms_per_step"] / 1e3) <= 0.01 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity"] is None
+    assert d["config"]["single_frame"] is None and d["config"]["frame_latency_ms"] is None
+    assert sum(d["config"]["launch_sizes"]) == 5
+    frames = sorted((tmp_path / "f").glob("frame_*.npy"), key=lambda p: int(p.stem.split("_")[1]))
+    assert len(frames) == 5
+    out = np.load(tmp_path / "o" / "frame.npy")
+    assert out.dtype == np.float32 and out.shape == (180, 320, 4)
+    assert np.array_equal(out, np.load(frames[-1]))
+    assert not np.array_equal(out, np.load(frames[-2]))  # the flyby: the last frame, not just any
 
 
 def test_workloads_match_baseline_configs():

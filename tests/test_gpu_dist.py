@@ -21,7 +21,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parents[1]
 ARGS = ["--width", "320", "--height", "180", "--max-steps", "800", "--steps", "12", "--warmup", "2",
-        "--inflight", "3", "--camera", "flyby", "--cpu-baseline", "off", "--critical-path", "off",
+        "--inflight", "3", "--camera", "flyby", "--full", "--cpu-baseline", "off", "--critical-path", "off",
         "--reference-loop", "off"]
 
 
@@ -89,7 +89,8 @@ def test_bench_gpus_2_without_a_launcher(tmp_path):
     GPU), labels the line with them, and its last timed headline frame matches
     the oracle's frame hashes."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo", "--steps", "4",
-                        "--warmup", "2", "--cpu-baseline", "off", "--critical-path", "off", "--reference-loop", "off"],
+                        "--warmup", "2", "--full", "--cpu-baseline", "off", "--critical-path", "off",
+                        "--reference-loop", "off"],
                        cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]

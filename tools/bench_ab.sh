@@ -14,7 +14,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
       a=${SETS[$k]}; [ "$a" = "-" ] && a=""
       lib=$V/variants/libsr_$n.so; [ "$n" = cur ] && lib=$V/libsr.so
       tag=${n}_a${k}_$r
-      SR_LIB=$lib timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-baseline off ${BENCH_ARGS:-} $a \
+      SR_LIB=$lib timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-baseline off ${BENCH_ARGS:-} $a \
         > "$OUT/$tag.log" 2>&1 || { tail -n 20 "$OUT/$tag.log"; exit 1; }
       grep '^{' "$OUT/$tag.log" > "$OUT/$tag.json"
       python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[2], d['value'], d['ms_per_step'], (d['config'].get('single_frame') or {}).get('alone', {}).get('ms_per_frame'))" "$OUT/$tag.json" "$tag [$a]"

@@ -50,7 +50,7 @@ def main():
            "--warmup", str(args.warmup), "--skybox", f"{tmp / 'sky.rgb'}:{sky.shape[1]}:{sky.shape[0]}",
            "--array", f"{tmp / 'arr.rgba'}:{a.shape[2]}:{a.shape[1]}:{a.shape[0]}", "--out-raw", str(tmp / "f.rgba")]
     bench = [sys.executable, str(ROOT / "bench.py"), "--steps", str(args.frames), "--batch", str(args.batch),
-             "--inflight", str(args.inflight), "--cpu-baseline", "off", "--critical-path", "off",
+             "--inflight", str(args.inflight), "--full", "--cpu-baseline", "off", "--critical-path", "off",
              "--reference-loop", "off", "--single-frame", "off"]
     with np.load(ROOT / "tests" / "golden" / "frame_hashes.npz") as z:
         rows, ref = z["c3/rows"], z["c3/rgba_sha"]

@@ -12,7 +12,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 export TMPDIR=/tmp
 OUT=gpurun_out/${SESSION:-roof}
 mkdir -p "$OUT"
-BENCH="bench.py --steps ${PMC_STEPS:-8} --warmup 4 --cpu-baseline off --critical-path off --reference-loop off ${BENCH_ARGS:-}"
+BENCH="bench.py --steps ${PMC_STEPS:-8} --warmup 4 --full --cpu-baseline off --critical-path off --reference-loop off ${BENCH_ARGS:-}"
 # HIP reads GPU_MAX_HW_QUEUES before bench.py runs when a profiler preloads it
 export GPU_MAX_HW_QUEUES=8
 step() {  # name timeout cmd...
@@ -36,7 +36,7 @@ cat "$OUT/pmc_flops.log"
 python tools/traffic_json.py --frame "$OUT/p3" "$OUT/p4" --out "$OUT/traffic_latest.json" ${SIZE_ARGS:-} > "$OUT/traffic.log" 2>&1 || { cat "$OUT/traffic.log"; exit 1; }
 # the headline bench line with the fresh counter files, under --stats
 cp "$OUT/pmc_latest.json" "$OUT/traffic_latest.json" /tmp/
-step stats 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --pmc-json /tmp/pmc_latest.json --traffic-json /tmp/traffic_latest.json --critical-path off ${BENCH_ARGS:-}
+step stats 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python bench.py --full --pmc-json /tmp/pmc_latest.json --traffic-json /tmp/traffic_latest.json --critical-path off ${BENCH_ARGS:-}
 grep '^{' "$OUT/stats.log" > "$OUT/bench_stats.json" || true
 python tools/trace_kernel_ms.py "$OUT/prof" --warmup 3 --steps ${STATS_STEPS:-96} --bench-json "$OUT/bench_stats.json" > "$OUT/kernel_ms_agreement.json" 2>&1
 cat "$OUT/kernel_ms_agreement.json"

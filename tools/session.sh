@@ -23,7 +23,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${SESSION:-session}
 mkdir -p "$OUT"
 V=${SR_VARIANTS:-$PWD/schwarzschild-raytracer_amd/lib/variants}  # lib/variants stays out of the GPU push (.gpurunignore): a session copies what it needs to lib/ab
-DRIVER="bench.py --gpus 1 --steps 20 --warmup 5"
+DRIVER="bench.py --gpus 1 --steps 20 --warmup 5 --full"  # --full: the steps below read the roofline, parity and single-frame figures
 
 step() {  # name timeout cmd... : logs to $OUT/name.log, stops the session on failure
   local name=$1 t=$2; shift 2
@@ -90,7 +90,7 @@ SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_IN
       python tools/pmc_summary.py "$OUT/pmc_$v"
     done ;;
   traffic)
-    B="bench.py --steps 8 --warmup 4 --cpu-baseline off --critical-path off --reference-loop off --single-frame off"
+    B="bench.py --steps 8 --warmup 4 --full --cpu-baseline off --critical-path off --reference-loop off --single-frame off"
     for n in $TRAFFIC; do
       for c in FETCH_SIZE WRITE_SIZE; do
         GPU_MAX_HW_QUEUES=8 SR_LIB=$V/libsr_$n.so step "traffic_${n}_$c" 180 rocprofv3 --kernel-trace --pmc $c -d "$OUT/$n-$c" -o run --output-format csv -- python $B

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 run() {  # name timeout bench-args...
   local name=$1 t=$2; shift 2
   echo "== $name: bench.py $*" | tee -a "$OUT/session.log"
-  timeout -k 10 "$t" python bench.py --cpu-baseline off --critical-path off "$@" > "$OUT/$name.log" 2>&1
+  timeout -k 10 "$t" python bench.py --full --cpu-baseline off --critical-path off "$@" > "$OUT/$name.log" 2>&1
   local rc=$?
   echo "== $name rc=$rc" | tee -a "$OUT/session.log"
   grep '^{' "$OUT/$name.log" >> "$OUT/variants.jsonl"
