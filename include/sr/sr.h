@@ -317,7 +317,8 @@ int sr_render_block_list(sr_ctx* ctx, const sr_camera* cams, int n_frames, const
  * cost-balanced multi-GPU shares: renders the frame (no image output, split
  * tiles off for this launch) and writes, for each 8x8 wave tile (row block
  * b = y / 8, column c = x / 8), dev_out[(b * ceil(width / 8) + c) * 2] = the
- * wave's longest ray's executed steps and [... + 1] = its budget events
+ * wave's longest ray's executed steps (a ray whose hit log filled counts with
+ * the steps the resume kernel ran for it too) and [... + 1] = its budget events
  * (DESIGN.md §5): int32 [ceil(height / 8)][ceil(width / 8)][2]. Deterministic,
  * so every rank of a node derives the same block lists from it. */
 int sr_wave_costs(sr_ctx* ctx, const sr_camera* cam, const sr_params* params, int width, int height,

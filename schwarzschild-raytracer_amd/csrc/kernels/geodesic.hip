@@ -3161,6 +3161,14 @@ __global__ __launch_bounds__(SR_WG) void sr_resume_kernel(const sr_dev_scene* __
         const size_t fo = (size_t)f * (size_t)fr.width * (size_t)fr.nrows;
         write_pixel(fr, out ? out + (size_t)f * (size_t)fr.out_frame_stride : nullptr, pitch,
                     dbg_rgba ? dbg_rgba + 4 * fo : nullptr, dbg_steps ? dbg_steps + fo : nullptr, q, frag, r.steps);
+        // sr_wave_costs: the integrate kernel stored the count at which this
+        // ray's hit log filled; the steps it ran here count for its 8x8 wave
+        // tile too (a max: the map stays deterministic). q is a pixel the
+        // shade kernel queued, so q.k < nrows and q.px < width.
+        if (fr.wave_cost) {
+            const int nb8 = (fr.nrows + 7) >> 3, nc8 = (fr.width + 7) >> 3;
+            atomicMax(fr.wave_cost + (((size_t)f * nb8 + (q.k >> 3)) * nc8 + (q.px >> 3)) * 2, r.steps);
+        }
     }
 }
 

@@ -184,3 +184,129 @@ def test_cylinder_hits_stay_on_the_lateral_surface(radius):
     fdev = frame_lateral_dev(p[hit], pos[hit], c0[hit], c2[hit], r[hit])
     ratio_len = fdev / lat_margin_len(seg32[hit].astype(np.float64), sc, radius)
     assert ratio_len.max() < 0.1, (ratio_len.max(), int(np.argmax(ratio_len)))
+
+
+def degenerate_axes(rng, n):
+    """Axes near (a, b, b) and (a, a, a), where the reference's gram_schmidt
+    of d.xzy, d, d.zxy starts from (nearly) parallel columns, perturbed by
+    1e-8 .. 1e-2 relative."""
+    a, b = rng.normal(size=n), rng.normal(size=n)
+    base = np.where((rng.random(n) < 0.5)[:, None], np.stack([a, b, b], 1), np.stack([a, a, a], 1))
+    eps = 10.0 ** rng.uniform(-8, -2, n)
+    return base * (1.0 + eps[:, None] * rng.normal(size=(n, 3)))
+
+
+def image_surface_distance(p, pos, M, Minv, r):
+    """binary64 distance of p from the M^-1 image of the frame's lateral
+    surface {x^2 + z^2 = r^2}: with q = M (p - pos), the minimum over the
+    surface's points s of |M^-1 (q - s)|. The free y takes out M^-1's middle
+    column; the rest is the distance from (q.x, q.z) to a circle in the
+    metric G of the other two columns, minimised over the circle's angle by
+    nested grids (any angle gives a point of the surface, so the value is
+    never below the true distance)."""
+    q = np.einsum("nij,nj->ni", M, p.astype(np.float64) - pos.astype(np.float64))
+    ay = Minv[:, :, 1]
+    lat = Minv[:, :, [0, 2]]
+    lat = lat - ay[:, :, None] * (np.einsum("ni,nik->nk", ay, lat) / np.sum(ay * ay, 1)[:, None])[:, None, :]
+    G = np.einsum("nik,nil->nkl", lat, lat)
+    v = q[:, [0, 2]]
+
+    def d2(theta):  # [n, k] angles -> squared distances
+        ex = v[:, 0, None] - r * np.cos(theta)
+        ez = v[:, 1, None] - r * np.sin(theta)
+        return G[:, 0, 0, None] * ex * ex + 2.0 * G[:, 0, 1, None] * ex * ez + G[:, 1, 1, None] * ez * ez
+
+    k0 = 256
+    theta = np.broadcast_to(np.arange(k0) * (2.0 * np.pi / k0), (len(p), k0))
+    val = d2(theta)
+    best = theta[np.arange(len(p)), np.argmin(val, 1)]
+    span = 2.0 * np.pi / k0
+    offs = np.linspace(-1.0, 1.0, 17)
+    for _ in range(9):  # the spacing ends below 1e-9 rad
+        theta = best[:, None] + span * offs[None, :]
+        val = d2(theta)
+        i = np.argmin(val, 1)
+        best = theta[np.arange(len(p)), i]
+        span /= 8.0
+    return np.sqrt(np.maximum(val[np.arange(len(p)), i], 0.0))
+
+
+@pytest.mark.parametrize("radius", [0.025, 0.3, 2.0])
+def test_skewed_frames_scale_the_lateral_margin(radius, capsys):
+    """The test ray's segment frames that are not orthonormal (ADVICE round
+    6, item 1): gram_schmidt_f32 of axes near (a, b, b) and (a, a, a) gives
+    frames M (rows c0, c1, c2) that fail orthonormal_f32, with condition
+    numbers up to ~1e6. cyl_test then tests the M^-1 image of the frame's
+    cylinder, and tr_bound_may_hit / clearance_tr (geodesic.hip) assume that
+    an accepted point lies within lat_margin_len(len, Sc, r) x |M^-1| |M|^2
+    of that image's lateral surface (spectral norms, sr_api.cpp frame_norms;
+    len, Sc of the chord in world coordinates). Grazing chords at every
+    angle to the axis are built in the frame's coordinates and mapped back
+    through M^-1; every accepted point's binary64 distance from the image
+    surface is held to that bound: ratio <= 1 is the condition the kernel
+    needs. Over the frames the host budgets (condition number below 1e3,
+    frame_norms) the worst ratio printed by this test was 0.017 (0.13 ..
+    0.36 without the scale, also printed: the scale buys a factor of ~20 on
+    these frames); the asserted 0.25 is the printed value with the factor of
+    4 the orthonormal case above keeps, and room for another seed."""
+    rng = np.random.default_rng(int(radius * 1000) + 11)
+    n = 270_000
+    c0, c1, c2 = gram_schmidt_f32(degenerate_axes(rng, n))
+    M = np.stack([c0, c1, c2], 1).astype(np.float64)  # local = M (world - pos)
+    with np.errstate(all="ignore"):
+        finite = np.isfinite(M).all((1, 2))
+        M = np.where(finite[:, None, None], M, np.eye(3))
+        sv = np.linalg.svd(M, compute_uv=False)
+        keep = finite & (sv[:, 2] > 0) & (sv[:, 0] / np.maximum(sv[:, 2], 1e-300) < 1e7)
+        keep &= ~orthonormal_f32(c0, c1, c2)
+    c0, c1, c2, M, sv = c0[keep], c1[keep], c2[keep], M[keep], sv[keep]
+    n = len(M)
+    assert n > 50_000, n
+    Minv = np.linalg.inv(M)
+    nm, ninv = sv[:, 0], 1.0 / sv[:, 2]
+    cond = nm * ninv
+    pos = rng.uniform(-20, 20, size=(n, 3)).astype(F)
+    height = F(1000.0) if radius < 0.1 else F(5.0)
+    r = np.full(n, radius, dtype=F)
+    # a grazing chord in the frame's coordinates (axis e_y), as in the test above
+    theta = 10.0 ** rng.uniform(-7, np.log10(np.pi / 2), size=n)
+    psi = rng.uniform(0, 2 * np.pi, n)
+    sgn = np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    dl = np.stack([np.sin(theta) * np.cos(psi), np.cos(theta) * sgn, np.sin(theta) * np.sin(psi)], 1)
+    perp = np.stack([-np.sin(psi), np.zeros(n), np.cos(psi)], 1)
+    delta = 10.0 ** rng.uniform(-9, -1, n) * np.where(rng.random(n) < 0.5, -1.0, 1.0)
+    rho = float(r[0]) * (1.0 + delta)
+    hgt = rng.uniform(-0.1, 1.1, n) * float(height if height < 100 else 20.0)
+    tp = perp * rho[:, None]
+    tp[:, 1] = hgt
+    segl = 10.0 ** rng.uniform(-2, np.log10(60.0), n)
+    ol = tp - dl * (segl * rng.uniform(-0.2, 1.2, n))[:, None]
+    # back to world coordinates through M^-1
+    o64 = pos.astype(np.float64) + np.einsum("nij,nj->ni", Minv, ol)
+    e64 = pos.astype(np.float64) + np.einsum("nij,nj->ni", Minv, ol + dl * segl[:, None])
+    seg = np.linalg.norm(e64 - o64, axis=1)
+    o = o64.astype(F)
+    d = ((e64 - o64) / seg[:, None]).astype(F)
+    seg32 = seg.astype(F)
+    with np.errstate(all="ignore"):
+        hit, p = cyl_test_f32(o, d, pos, c0, c1, c2, height, r, seg32)
+    hit &= np.isfinite(p).all(1)
+    assert hit.sum() > 10_000, hit.sum()
+    dist = image_surface_distance(p[hit], pos[hit], M[hit], Minv[hit], float(r[0]))
+    sc = np.abs(o[hit].astype(np.float64)).sum(1) + seg32[hit].astype(np.float64) + 1.0 + \
+        np.abs(pos[hit].astype(np.float64)).sum(1)
+    bound = lat_margin_len(seg32[hit].astype(np.float64), sc, radius) * ninv[hit] * nm[hit] ** 2
+    ratio = dist / bound
+    budgeted = cond[hit] < 1e3  # the frames frame_norms accepts
+    assert budgeted.sum() > 5_000, budgeted.sum()
+    with capsys.disabled():
+        print(f"\nr = {radius}: {n} skewed frames (condition up to {cond.max():.3g}), {int(hit.sum())} accepted points "
+              f"({int(budgeted.sum())} in budgeted frames); worst ratio {ratio.max():.4f} overall, "
+              f"{ratio[budgeted].max():.4f} in budgeted frames (without the scale: "
+              f"{(ratio * ninv[hit] * nm[hit] ** 2)[budgeted].max():.3g})")
+    # the condition the kernel needs, for every frame
+    assert ratio.max() <= 1.0, (ratio.max(), int(np.argmax(ratio)))
+    # and a safety factor of 4 over the frames the host budgets
+    assert ratio[budgeted].max() < 0.25, ratio[budgeted].max()
+    # near-parallel chords are among the accepted ones
+    assert (theta[hit] < 1e-3).sum() > 100
