@@ -104,6 +104,40 @@ typedef struct {
     float a2[3], cn;  // cn: |bc| x 1.001, rounded up (outward_clear)
 } sr_dev_slot;  // 128 B
 
+// The start table (geodesic.hip sr_start_table_kernel, budget_start): what a
+// ray's first budgets take from the camera alone, computed once per launch
+// for every frame of the batch by the device functions the budget events
+// use (hardware sqrt / rcp: the host cannot), instead of by each of the
+// frame's waves. One record per frame, read with wave-uniform loads.
+// Budgeted cylinders with slab budgets (the kernel's NC; none by default)
+#define SR_START_CYL 4
+// flags of a slot
+#define SR_START_OUT 1  // an outward lane's budget is +inf (outward_slot)
+#define SR_START_WIN 2  // the directional start window applies (plane_window_dir)
+typedef struct {
+    float e;         // clearance_obj(slot, camera) - m0 (max with 0 where the start window gives 0)
+    float k2r;       // the start window's 2 kap R
+    float need;      // xplane_need (+inf: never excluded)
+    int32_t flags;   // SR_START_*
+    float bc[3];     // the bounding centre (the orbital-plane exclusions)
+    float xneed;     // sr_dev_frame.xlow_need[j - 1]
+    float wn[3];     // the plane's normal, turned against the camera's side
+    float xperi;     // sr_dev_frame.xperi_e[j - 1]
+} sr_dev_start_slot;  // 48 B
+typedef struct {
+    float nv[3];     // nrm(pos) (init_pixel)
+    float u;         // 1 / len(pos)
+    float a;         // |pos|, hardware sqrt (budget_init)
+    float cx;        // pos . nv: the ball's centre along nv
+    float e_bh[2];   // slot 0's budget less m0, for a lane not falling / falling (bh_start)
+    float uhi[2];    // its u window's bound, likewise
+    float e_tr[2];   // the test ray's budget less m0, for a lane not outward / outward (clearance_tr)
+    int32_t bh_out;  // 1: an outward lane has passed the hole (outward_clear)
+    float kap, a2s, cap;  // the start windows' camera-only constants (plane_window_cam)
+    float slab[SR_START_CYL];  // the k-th budgeted cylinder's slab budget less m0
+    sr_dev_start_slot slot[SR_MAX_BUDGET];  // budget slots 1..num_budget
+} sr_dev_start;
+
 // Per-pixel state passed between the integrate / shade / resume kernels
 // (geodesic.hip PS_*), floats per pixel: a 16-byte record {packed word
 // (status, hit count, steps), rd[3]}, SR_PS_HITS 32-byte hit

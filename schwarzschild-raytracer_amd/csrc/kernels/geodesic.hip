@@ -479,7 +479,7 @@ __device__ __forceinline__ float plane_window(const sr_dev_slot& sl, f3 A, f3 B,
     const float f = 1.0f - (th1 * th1 + th1 * th0 + th0 * th0) * (1.0f / 6.0f);
     return (Lc > 0.0f && f > 0.0f) ? Lc * f * 0.998f : 0.0f;
 }
-// The same window from a ray's start (budget_init): the anchor A is the
+// The same window from a ray's start (budget_start): the anchor A is the
 // camera (or a reseed point), where the orbit's tangent is the ray direction
 // d itself (the frame nv, tv and u' = -u (d . nv) / (d . tv) are built from
 // it: the tangent (nv cos phi + tv sin phi) / u differentiated at phi = 0 is
@@ -490,21 +490,49 @@ __device__ __forceinline__ float plane_window(const sr_dev_slot& sl, f3 A, f3 B,
 #ifndef SR_INIT_WINDOW
 #define SR_INIT_WINDOW 1
 #endif
-__device__ __forceinline__ float plane_window_start(const sr_dev_slot& sl, f3 A, f3 d, float a, float perr, float dphi) {
+// Split for the start table (sr_start_table_kernel, budget_start): the camera
+// half runs once per frame, the direction half per ray, each operation where
+// it was and in the same order. One reordering: the side's sign moves from
+// the product (y > 0 ? -1 : 1) * dot(d, n) into the normal, wn = n * (+-1).
+// Scaling by +-1 is exact, and rounding to nearest is symmetric, so every
+// product and partial sum of dot(d, -n) is the negation of dot(d, n)'s:
+// dot(d, wn) has the same bits (up to the sign of a zero, which b = c + th0
+// absorbs, and of a NaN).
+struct PlaneWinCam {
+    bool ok;    // false: the window is 0
+    f3 wn;      // the normal, turned against the camera's side
+    float k2r;  // 2 kap R
+    float kap, a2s, cap;  // 6.06 / a^2, a^2 / 6.06 and the caps of Lc: the same for every slot
+};
+__device__ __forceinline__ PlaneWinCam plane_window_cam(const sr_dev_slot& sl, f3 A, float a, float perr, float dphi) {
+    PlaneWinCam w;
+    w.ok = false;
+    w.wn = F3(0.0f, 0.0f, 0.0f);
+    w.k2r = w.kap = w.a2s = w.cap = 0.0f;
     const f3 nrm_ = ld3(sl.a1);
     const float y = dot(A - ld3(sl.pos), nrm_);
-    if (!(a > 1.0f)) return 0.0f;
+    if (!(a > 1.0f)) return w;
     const float a2 = a * a;
     const float kap = 6.06f * __builtin_amdgcn_rcpf(a2);  // 6 / a^2 plus 1 %
-    const float c = (y > 0.0f ? -1.0f : 1.0f) * dot(d, nrm_);
+    w.wn = nrm_ * (y > 0.0f ? -1.0f : 1.0f);
     const float th0 = 1e-4f;
     const float m = (sl.mp + sl.mu * __builtin_fmaf(3.1f, a, 1.0f)) * 1.001f + perr;  // S <= 3.1 a + 1 (planar)
     const float R = fabsf(y) - m;
-    if (!(R > 0.0f)) return 0.0f;
-    const float b = c + th0;
-    const float L = (__builtin_amdgcn_sqrtf(__builtin_fmaf(b, b, 2.0f * kap * R)) - b) * (a2 * (1.0f / 6.06f));
+    if (!(R > 0.0f)) return w;
+    w.k2r = 2.0f * kap * R;
+    w.kap = kap;
+    w.a2s = a2 * (1.0f / 6.06f);
     const float ch = 1.5f * a * dphi;  // the next chord
-    const float Lc = fminf(L, fminf(__builtin_fmaf(0.5f, a, -ch), (1.5f - th0) * (a2 * (1.0f / 6.06f)) - ch));
+    w.cap = fminf(__builtin_fmaf(0.5f, a, -ch), (1.5f - th0) * (a2 * (1.0f / 6.06f)) - ch);
+    w.ok = true;
+    return w;
+}
+__device__ __forceinline__ float plane_window_dir(f3 wn, float k2r, float kap, float a2s, float cap, f3 d) {
+    const float c = dot(d, wn);
+    const float th0 = 1e-4f;
+    const float b = c + th0;
+    const float L = (__builtin_amdgcn_sqrtf(__builtin_fmaf(b, b, k2r)) - b) * a2s;
+    const float Lc = fminf(L, cap);
     const float th1 = __builtin_fmaf(kap, Lc, th0);
     const float f = 1.0f - (th1 * th1 + th1 * th0 + th0 * th0) * (1.0f / 6.0f);
     return (Lc > 0.0f && f > 0.0f) ? Lc * f * 0.998f : 0.0f;
@@ -816,12 +844,21 @@ struct Budget {
 // (xs = sr_dev_frame.xplane_s: S_max of the orbit's chords, +inf: no
 // exclusion; it carries 0.5 % on top, which covers the end points' 4e-7 r
 // off the plane as mu >= SR_MU_PLANAR)
-__device__ __forceinline__ uint32_t xplane_bit(const sr_dev_slot& sl, int j, f3 n, float nn, float xs) {
-    if (sl.type == SR_OBJECT_PLANE || sl.type == SR_OBJECT_CYLINDER) return 0u;
-    const float h = dot(ld3(sl.bc), n);  // |h| / |n|: bc's distance from the plane
-    const float need = (sl.br + sl.mu * xs) * 1.001f + 1.0e-4f + 1.0e-5f * sl.cn;
+// (the slot's half, +inf where nothing is excluded, apart from the orbit's:
+// the start table holds the first per frame)
+__device__ __forceinline__ float xplane_need(const sr_dev_slot& sl, float xs) {
+    if (sl.type == SR_OBJECT_PLANE || sl.type == SR_OBJECT_CYLINDER) return INFINITY;
+    return (sl.br + sl.mu * xs) * 1.001f + 1.0e-4f + 1.0e-5f * sl.cn;
+}
+// bc farther than `need` from the orbital plane
+__device__ __forceinline__ uint32_t plane_off_bit(f3 bc, int j, f3 n, float nn, float need) {
+    const float h = dot(bc, n);  // |h| / |n|: bc's distance from the plane
     // |h| / sqrt(nn) > need without a square root; NaN frames exclude nothing
+    // (nor does need = +inf: nothing exceeds +inf, and +inf x 0 is NaN)
     return (uint32_t)(h * h > (need * need) * (nn * 1.0002f)) << j;
+}
+__device__ __forceinline__ uint32_t xplane_bit(const sr_dev_slot& sl, int j, f3 n, float nn, float xs) {
+    return plane_off_bit(ld3(sl.bc), j, n, nn, xplane_need(sl, xs));
 }
 // A bounded slot off a low-energy orbit's plane (SR_XCYL): need =
 // sr_dev_frame.xlow_need[j - 1] (sr_api.cpp xlow_need has the bound: the
@@ -834,8 +871,7 @@ __device__ __forceinline__ uint32_t xplane_bit(const sr_dev_slot& sl, int j, f3 
 #define SR_XCYL 1
 #endif
 __device__ __forceinline__ uint32_t xcyl_bit(const sr_dev_slot& sl, int j, f3 n, float nn, float need) {
-    const float h = dot(ld3(sl.bc), n);
-    return (uint32_t)(h * h > (need * need) * (nn * 1.0002f)) << j;
+    return plane_off_bit(ld3(sl.bc), j, n, nn, need);
 }
 // The orbit's energy E = u'^2 + u^2 (1 - u) for the exclusions of low-energy
 // orbits (SR_XCYL, SR_XPERI: u < 0.6 and E <= SR_XCYL_EMAX), +inf otherwise
@@ -918,13 +954,30 @@ __device__ __forceinline__ bool cyl_par_bit(const sr_dev_scene* __restrict__ sc,
 __device__ float clearance_tr(const sr_dev_scene* __restrict__ sc, const float* __restrict__ segs, f3 A, bool outward,
                               float a, float dip, float rlen, uint32_t& gm);
 
-// START_WINDOW: d is the orbit's tangent at A (a ray's start, sr_integrate_kernel),
-// so the planar slots may take plane_window_start's directional budget
-template <bool START_WINDOW, class BS>
+// Slot 0's budget at an anchor at distance a, before the outward lanes'
+// exclusion and m0; uhi: the lane's u window (SR_BH_WINDOW, SR_BH_WINDOW2)
+__device__ __forceinline__ float bh_start(float a, float dip, bool bh_ok, bool falling, float u2w, float& uhi) {
+    float e = clearance_bh(a);
+    uhi = SR_U_NOWIN;
+    if (SR_BH_WINDOW && bh_ok && a > SR_BH_RWIN) {
+        e = INFINITY;
+        uhi = SR_BH_U;
+    }
+    if (SR_BH_WINDOW2 && dip > SR_BH_DIP2 && a * u2w > 1.000001f && a < SR_BH_RMAX2 && (falling || !(a > SR_BH_RWIN))) {
+        e = INFINITY;
+        uhi = u2w;
+    }
+    return e;
+}
+
+// The budgets at an anchor A of a lane's own (sr_resume_kernel: the point
+// where the ray resumes; its direction is a chord's, not the orbit's tangent,
+// so no start window). A ray's start at the camera is budget_start's.
+template <class BS>
 __device__ __forceinline__ void budget_init(const sr_dev_scene* __restrict__ sc, const float* __restrict__ segs,
                                             BS& bs, f3 A, f3 nv, f3 tv,
                                             bool outward, float dip, bool bh_ok, bool falling, float xs, float u2w,
-                                            const float* xneed, const float* xperi, float eo, f3 d, float dphi) {
+                                            const float* xneed, const float* xperi, float eo) {
     const float a = __builtin_amdgcn_sqrtf(dot(A, A));
     const int nb = sc->num_budget;
     bs.setT(0.0f);
@@ -940,16 +993,8 @@ __device__ __forceinline__ void budget_init(const sr_dev_scene* __restrict__ sc,
     const float xnn = dot(xn, xn);
     uint32_t xcl = 0;
     {
-        float e = clearance_bh(a);
-        float uhi = SR_U_NOWIN;
-        if (SR_BH_WINDOW && bh_ok && a > SR_BH_RWIN) {
-            e = INFINITY;
-            uhi = SR_BH_U;
-        }
-        if (SR_BH_WINDOW2 && dip > SR_BH_DIP2 && a * u2w > 1.000001f && a < SR_BH_RMAX2 && (falling || !(a > SR_BH_RWIN))) {
-            e = INFINITY;
-            uhi = u2w;
-        }
+        float uhi;
+        float e = bh_start(a, dip, bh_ok, falling, u2w, uhi);
         bs.setUhi(uhi);
         if (outward && outward_clear(1.0f, 0.0f, SR_MU_QUADRATIC, 0.0f, 0.0f, a, dip)) e = INFINITY;
         e -= m0;
@@ -975,12 +1020,6 @@ __device__ __forceinline__ void budget_init(const sr_dev_scene* __restrict__ sc,
         if (SR_XCYL && eo <= SR_XCYL_EMAX) xcl |= xcyl_bit(sl, j, xn, xnn, xneed[j - 1]);
         if (SR_XPERI && eo <= xperi[j - 1]) xcl |= 1u << j;
         float e = clearance_obj(sl, A, a) - m0;
-        if (START_WINDOW && SR_INIT_WINDOW && (sl.type == SR_OBJECT_RECTANGLE || sl.type == SR_OBJECT_DISK ||
-                               sl.type == SR_OBJECT_HOLLOW_DISK || sl.type == SR_OBJECT_PLANE) &&
-            sl.mp < INFINITY && e < 0.5f * a) {
-            const float w = plane_window_start(sl, A, d, a, m0, dphi);
-            e = w > e ? w : e;  // NaN e stays NaN
-        }
         if (outward && outward_slot(sl, cyl_par_bit(sc, bs, j), a, dip)) e = INFINITY;
         if ((xcl >> j) & 1u) e = INFINITY;  // off this orbit's plane (budget_frame)
         bs.E[j * SR_E_STRIDE] = e;
@@ -994,6 +1033,193 @@ __device__ __forceinline__ void budget_init(const sr_dev_scene* __restrict__ sc,
     for (int k = 0; k < BS::NC; k++) {
         if (c) {
             const float e = clearance_slab(sc->slots[__builtin_ctz(c)], A, a) - m0;
+            bs.E[(BS::L::SLAB0 + k) * SR_E_STRIDE] = e;
+            mh = nmin(mh, e);
+            c &= c - 1;
+        }
+    }
+    bs.setMh(mh);
+}
+
+// The start table (sr_dev_start). Every ray of a frame starts at the camera,
+// so budget_init at that anchor gave each of the frame's waves the same
+// clearances from the same inputs: a tenth of the headline frame's
+// wave-cycles (SR_PROF section 22), most of it waiting for the slots' 128-byte
+// records. build_start computes the camera-only part once per frame and
+// launch (sr_start_table_kernel), with the functions the events call and in
+// budget_init's order; budget_start is the ray's part. -ffp-contract=off: the
+// same call rounds the same in either kernel. The __ballot in clearance_obj
+// and clearance_tr sees one value of a wave-uniform condition in both.
+// outward_slot must not depend on the lane's orbital plane (cyl_par):
+static_assert(SR_OUT_CYL_CM == 1, "the start table holds outward_slot per camera: keep cyl_par per ray otherwise");
+__device__ void build_start(const sr_dev_scene* __restrict__ sc, const float* __restrict__ segs, const sr_dev_frame& fr,
+                            f3 A, sr_dev_start& o) {
+    // init_pixel's camera-only values (frag:883-887)
+    const f3 nv = nrm(A);
+    o.nv[0] = nv.x;
+    o.nv[1] = nv.y;
+    o.nv[2] = nv.z;
+    o.u = 1.0f / len(A);
+    const float a = __builtin_amdgcn_sqrtf(dot(A, A));
+    const float m0 = 2.0e-6f * (a + 1.0f);
+    const float dip = fr.out_dip;
+    o.a = a;
+    o.cx = dot(A, nv);
+    for (int falling = 0; falling < 2; falling++) {
+        float uhi;
+        const float e = bh_start(a, dip, fr.win_ok && fr.out_dip > SR_BH_DIP, falling != 0, fr.bh_u2, uhi);
+        o.e_bh[falling] = e - m0;
+        o.uhi[falling] = uhi;
+    }
+    o.bh_out = outward_clear(1.0f, 0.0f, SR_MU_QUADRATIC, 0.0f, 0.0f, a, dip) ? 1 : 0;
+    for (int outward = 0; outward < 2; outward++) {
+        uint32_t gm;
+        o.e_tr[outward] = fr.tr_visible ? clearance_tr(sc, segs, A, outward != 0, a, dip, -1.0f, gm) - m0 : 0.0f;
+    }
+    o.kap = o.a2s = o.cap = 0.0f;
+    int nb = sc->num_budget;
+    nb = nb < SR_MAX_BUDGET ? nb : SR_MAX_BUDGET;
+    for (int j = 0; j < nb; j++) {
+        const sr_dev_slot& sl = sc->slots[j];
+        sr_dev_start_slot& t = o.slot[j];
+        float e = clearance_obj(sl, A, a) - m0;
+        int flags = 0;
+        f3 wn = F3(0.0f, 0.0f, 0.0f);
+        float k2r = 0.0f;
+        // the planar slots' directional start window (the camera's half)
+        if (SR_INIT_WINDOW && (sl.type == SR_OBJECT_RECTANGLE || sl.type == SR_OBJECT_DISK ||
+                               sl.type == SR_OBJECT_HOLLOW_DISK || sl.type == SR_OBJECT_PLANE) &&
+            sl.mp < INFINITY && e < 0.5f * a) {
+            const PlaneWinCam w = plane_window_cam(sl, A, a, m0, fr.max_dphi);
+            if (w.ok) {
+                flags |= SR_START_WIN;
+                wn = w.wn;
+                k2r = w.k2r;
+                // functions of a and max_dphi alone: every slot's are the same
+                o.kap = w.kap;
+                o.a2s = w.a2s;
+                o.cap = w.cap;
+            } else {
+                const float w0 = 0.0f;  // the window every ray would get
+                e = w0 > e ? w0 : e;    // NaN e stays NaN
+            }
+        }
+        if (outward_slot(sl, false, a, dip)) flags |= SR_START_OUT;
+        t.e = e;
+        t.k2r = k2r;
+        t.need = SR_XPLANE ? xplane_need(sl, fr.xplane_s) : INFINITY;
+        t.flags = flags;
+        t.bc[0] = sl.bc[0];
+        t.bc[1] = sl.bc[1];
+        t.bc[2] = sl.bc[2];
+        t.xneed = fr.xlow_need[j];
+        t.wn[0] = wn.x;
+        t.wn[1] = wn.y;
+        t.wn[2] = wn.z;
+        t.xperi = fr.xperi_e[j];
+    }
+    uint32_t c = (uint32_t)sc->budget_cyl_mask;
+    for (int k = 0; k < SR_START_CYL; k++) {
+        o.slab[k] = INFINITY;
+        if (c) {
+            o.slab[k] = clearance_slab(sc->slots[__builtin_ctz(c)], A, a) - m0;
+            c &= c - 1;
+        }
+    }
+}
+
+// A start slot's record in one batch of scalar loads (as pin_slot)
+__device__ __forceinline__ sr_dev_start_slot pin_start_slot(const sr_dev_start_slot& g) {
+    sr_dev_start_slot t = g;
+    SR_PIN(t.e);
+    SR_PIN(t.k2r);
+    SR_PIN(t.need);
+    SR_PIN(t.flags);
+    SR_PIN(t.bc[0]);
+    SR_PIN(t.bc[1]);
+    SR_PIN(t.bc[2]);
+    SR_PIN(t.xneed);
+    SR_PIN(t.wn[0]);
+    SR_PIN(t.wn[1]);
+    SR_PIN(t.wn[2]);
+    SR_PIN(t.xperi);
+    return t;
+}
+
+// A ray's start at the camera (sr_integrate_kernel): budget_init's LDS rows
+// from the frame's start record st (wave-uniform: one frame per workgroup)
+// and the ray's own part: its orbital plane's exclusions, outward / falling,
+// and the start windows' direction half. d: the ray direction, the orbit's
+// tangent at the camera.
+template <class BS>
+__device__ __forceinline__ void budget_start(const sr_dev_scene* __restrict__ sc, const sr_dev_start& st, BS& bs, int nb,
+                                             f3 A, f3 nv, f3 tv, bool outward, bool falling, float eo, f3 d) {
+    static_assert(BS::NC <= SR_START_CYL, "sr_dev_start.slab holds SR_START_CYL cylinders");
+    // slot 1's record is in flight while the header's rows are stored, slot
+    // j + 1's while slot j is worked on (as budget_init)
+    sr_dev_start_slot nxt;
+    if (nb > 0) nxt = st.slot[0];
+    bs.setT(0.0f);
+    bs.setC(st.cx, dot(A, tv));
+    float m = INFINITY;
+    const uint32_t cm = budget_cyl_frame(sc, bs, nv, tv);
+    const f3 xn = cross(nv, tv);
+    const float xnn = dot(xn, xn);
+    uint32_t xcl = 0;
+    // the header in one batch of scalar loads, both values of a per-lane
+    // choice (a select between two SGPRs, not a load through a per-lane address)
+    float e0 = st.e_bh[0], e1 = st.e_bh[1], uh0 = st.uhi[0], uh1 = st.uhi[1];
+    float kap = st.kap, a2s = st.a2s, cap = st.cap;
+    int bh_out = st.bh_out;
+    SR_PIN(e0);
+    SR_PIN(e1);
+    SR_PIN(uh0);
+    SR_PIN(uh1);
+    SR_PIN(kap);
+    SR_PIN(a2s);
+    SR_PIN(cap);
+    SR_PIN(bh_out);
+    {
+        float e = falling ? e1 : e0;
+        bs.setUhi(falling ? uh1 : uh0);
+        if (outward && bh_out) e = INFINITY;  // (+inf - m0 = +inf)
+        bs.E[0] = e;
+        m = nmin(m, e);
+    }
+    if constexpr (BS::TR) {
+        float t0 = st.e_tr[0], t1 = st.e_tr[1];
+        SR_PIN(t0);
+        SR_PIN(t1);
+        const float e = outward ? t1 : t0;
+        bs.setEtr(e);
+        m = nmin(m, e);
+    }
+#pragma unroll 1
+    for (int j = 1; j <= nb; j++) {
+        const sr_dev_start_slot t = pin_start_slot(nxt);
+        if (j < nb) nxt = st.slot[j];
+        const f3 bc = ld3(t.bc);
+        if (SR_XPLANE) xcl |= plane_off_bit(bc, j, xn, xnn, t.need);
+        if (SR_XCYL && eo <= SR_XCYL_EMAX) xcl |= plane_off_bit(bc, j, xn, xnn, t.xneed);
+        if (SR_XPERI && eo <= t.xperi) xcl |= 1u << j;
+        float e = t.e;
+        if (t.flags & SR_START_WIN) {
+            const float w = plane_window_dir(ld3(t.wn), t.k2r, kap, a2s, cap, d);
+            e = w > e ? w : e;  // NaN e stays NaN
+        }
+        if (outward && (t.flags & SR_START_OUT)) e = INFINITY;
+        if ((xcl >> j) & 1u) e = INFINITY;  // off this orbit's plane (budget_frame)
+        bs.E[j * SR_E_STRIDE] = e;
+        m = nmin(m, e);
+    }
+    bs.setCm(cm, xcl);
+    bs.setM(m);
+    float mh = INFINITY;
+    uint32_t c = (uint32_t)sc->budget_cyl_mask;
+#pragma unroll
+    for (int k = 0; k < BS::NC; k++) {
+        if (c) {
+            const float e = st.slab[k];
             bs.E[(BS::L::SLAB0 + k) * SR_E_STRIDE] = e;
             mh = nmin(mh, e);
             c &= c - 1;
@@ -2152,14 +2378,17 @@ __device__ __forceinline__ f4 crosshair_frag(const sr_dev_frame& fr, const Pix& 
 
 // frag:859-889: camera ray, flat / percent_black early outs and the initial
 // (u, du) of the geodesic. Returns ST_FLAT, ST_DONE or -1 (integrate).
-__device__ __forceinline__ int init_pixel(const sr_dev_frame& fr, const sr_dev_cam& cam, const Pix& q, Ray& r) {
+// st: the frame's start record, which holds nrm(ro) and 1 / len(ro) (build_start:
+// the same expressions on the camera position, once per frame)
+__device__ __forceinline__ int init_pixel(const sr_dev_frame& fr, const sr_dev_cam& cam, const sr_dev_start& st,
+                                          const Pix& q, Ray& r) {
     // full_screen_quad.vert:7-10: uv = NDC of the pixel centre
     f2 uv = F2((float)(2 * q.px + 1) / (float)fr.width - 1.0f, (float)(2 * q.py + 1) / (float)fr.height - 1.0f);
     f2 uvv = F2(uv.x, uv.y * fr.res_y / fr.res_x);
     m3 axes = ldm(cam.axes);
     r.ro = ld3(cam.pos);
     r.rd = nrm(mv(axes, F3(uvv.x, uvv.y, cam.ray_forward)));
-    r.nv = nrm(r.ro);
+    r.nv = ld3(st.nv);
     r.steps = 0;
     r.i = 0;
     SR_PROBE(probe_ray_init(r));
@@ -2173,7 +2402,7 @@ __device__ __forceinline__ int init_pixel(const sr_dev_frame& fr, const sr_dev_c
     }
     // frag:883-889
     r.tv = nrm(cross(cross(r.nv, r.rd), r.nv));
-    r.u = 1.0f / len(r.ro);
+    r.u = st.u;
     r.du = -r.u * dot(r.rd, r.nv) / dot(r.rd, r.tv);
     return -1;
 }
@@ -2292,25 +2521,29 @@ template <bool CULL, bool RECORD, bool WCOST = false, int NB = SR_MAX_BUDGET, in
           int NC = SR_NC_KERNEL, bool TR = false>
 __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, const float* __restrict__ segs,
                                          const float4* __restrict__ tbl, const sr_dev_frame& fr, const Tex& tx,
-                                         Ray& r, Hit& hit, HitLog& log) {
+                                         Ray& r, Hit& hit, HitLog& log, const sr_dev_start* __restrict__ start = nullptr) {
     using BS = Budget<NB, NC, TR && CULL>;
     __shared__ float lds_E[BS::L::ROWS * SR_E_STRIDE];  // blockDim.x == SR_E_STRIDE
     BS bs;
     bs.E = lds_E + threadIdx.x;
     SR_PROBE(SR_PROF_CLOCK(prof_bi_));  // budget_init's cycles (section 22)
     if (!CULL) bs.setUhi(INFINITY);
-    if (CULL)
-        // the ray's start (sr_integrate_kernel): r.rd is the orbit's tangent at
-        // r.ro; a resumed ray's is a chord direction, so no start window. (Round
+    if constexpr (CULL && RECORD)
+        // the ray's start (sr_integrate_kernel) at the camera, from the frame's
+        // start record; r.rd is the orbit's tangent at r.ro
+        budget_start(sc, *start, bs, fr.num_budget, r.ro, r.nv, r.tv, r.du < 0.0f && r.u < 0.6f, r.du > 0.0f,
+                     orbit_e(r.u, r.du), r.rd);
+    else if (CULL)
+        // a resumed ray's r.rd is a chord direction, so no start window. (Round
         // 6: the resume passed a NaN direction "to get 0", but fminf drops a NaN
-        // operand, and plane_window_start returned its caps: a window toward a
+        // operand, and the start window (plane_window_dir) returned its caps: a window toward a
         // plane the resumed ray was heading into, missing its hit whenever no
         // wave-mate's event re-anchored the slot first - three pixels of a
         // four-frame batch of the stress scene, varying run to run with the
         // worklist's order, tests/test_gpu_parity.py test_resumed_rays_*.)
-        budget_init<RECORD>(sc, segs, bs, r.ro, r.nv, r.tv, r.du < 0.0f && r.u < 0.6f, fr.out_dip,
-                            fr.win_ok && fr.out_dip > SR_BH_DIP, r.du > 0.0f, fr.xplane_s, fr.bh_u2, fr.xlow_need,
-                            fr.xperi_e, orbit_e(r.u, r.du), r.rd, fr.max_dphi);
+        budget_init(sc, segs, bs, r.ro, r.nv, r.tv, r.du < 0.0f && r.u < 0.6f, fr.out_dip,
+                    fr.win_ok && fr.out_dip > SR_BH_DIP, r.du > 0.0f, fr.xplane_s, fr.bh_u2, fr.xlow_need,
+                    fr.xperi_e, orbit_e(r.u, r.du));
     SR_PROBE(FireProbe<Ray, BS> fire_probe_(r, bs));
     const int N = fr.max_steps;
     // every chord is tested exactly when objects outside the budget slots or
@@ -2857,6 +3090,15 @@ __device__ __forceinline__ int split_thread(int sub, int tid, int lg) {
     return quad * 64 + y8 * 8 + x8;
 }
 
+// One thread per frame of the batch: frame f's start record (build_start)
+__global__ __launch_bounds__(64) void sr_start_table_kernel(const sr_dev_scene* __restrict__ sc,
+                                                            const float* __restrict__ segs, sr_dev_frame fr,
+                                                            sr_dev_start* __restrict__ start) {
+    const int f = (int)blockIdx.x;
+    if (f >= fr.batch || threadIdx.x != 0) return;
+    build_start(sc, segs, fr, ld3(fr.cam[f].pos), start[f]);
+}
+
 // 1-D grid: workgroup s = (slot * B + f) * SR_WG_PER_TILE + part renders
 // part `part` (SR_WG threads) of launch code order[slot] of frame f of the
 // batch (costliest tiles of every frame first, order_tiles), and records
@@ -2873,7 +3115,8 @@ template <bool CULL, bool WCOST = false, int NB = SR_MAX_BUDGET, int FU = SR_FAS
 __global__ __launch_bounds__(SR_WG, sr_integrate_waves(NB, NC)) void sr_integrate_kernel(
     const sr_dev_scene* __restrict__ sc, const float4* __restrict__ tbl, const float* __restrict__ segs,
     const uint32_t* __restrict__ arr, const uint8_t* __restrict__ opq, sr_dev_frame fr, float* __restrict__ ps_base,
-    size_t ps_n, int* __restrict__ count, const int* __restrict__ order, int* __restrict__ cost) {
+    size_t ps_n, int* __restrict__ count, const int* __restrict__ order, int* __restrict__ cost,
+    const sr_dev_start* __restrict__ start) {
     const unsigned B = (unsigned)fr.batch;
     const unsigned bid = blockIdx.x;
     const unsigned wg = bid / SR_WG_PER_TILE;  // the tile's workgroup index (slot * B + f)
@@ -2911,9 +3154,9 @@ __global__ __launch_bounds__(SR_WG, sr_integrate_waves(NB, NC)) void sr_integrat
         const PS& ps = log.ps;
         Ray r;
         Hit hit;
-        int st = init_pixel(fr, fr.cam[frame], q, r);
+        int st = init_pixel(fr, fr.cam[frame], start[frame], q, r);
         SR_PROBE(st = wp.lane_mask(q.px, q.py, fr.width, st, ST_DONE); wp.ray_start(r));
-        if (st < 0) st = integrate<CULL, true, WCOST, NB, FU, NC, TR>(sc, segs, tbl, fr, tx, r, hit, log);
+        if (st < 0) st = integrate<CULL, true, WCOST, NB, FU, NC, TR>(sc, segs, tbl, fr, tx, r, hit, log, start + frame);
         const size_t id = log.id();
         ps.put_rec(id, ps_word(st, log.n, r.steps), r.rd);
         SR_PROBE(wp.pixel(st, log.n));
@@ -3178,7 +3421,8 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
                                          const uint32_t* bg, const uint32_t* arr, const uint8_t* opq,
                                          const sr_dev_frame* fr, uint8_t* out, size_t pitch, float* dbg_rgba,
                                          int32_t* dbg_steps, float* ps, size_t ps_n, int* list, int* count,
-                                         int* order, int* cost, int* diag, hipEvent_t* ev4, hipStream_t stream) {
+                                         int* order, int* cost, int* diag, sr_dev_start* start, hipEvent_t* ev4,
+                                         hipStream_t stream) {
     dim3 block(256);
     dim3 grid((fr->width + 15) / 16, (fr->nrows + 15) / 16);
     if (grid.x == 0 || grid.y == 0) return hipSuccess;
@@ -3202,43 +3446,47 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
     // cylinders with direction tests beyond what the instantiations handle (a
     // host built with SR_CYL_DIRFREE=0 against a kernel without them)
     if (cull && fr->num_budget_cyl > SR_NC_KERNEL && !small) return hipErrorInvalidValue;
+    if (!start) return hipErrorInvalidValue;
     if (ev4) (void)hipEventRecord(ev4[0], stream);
+    // the frames' start records, on every launch (the cameras, the scene and
+    // the schedule are the launch's own; the integrate time includes it)
+    hipLaunchKernelGGL(sr_start_table_kernel, dim3(B), dim3(1), 0, stream, sc, segs, *fr, start);
     if (fr->wave_cost && general)
         hipLaunchKernelGGL((sr_integrate_kernel<true, true, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>),
                            dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream,
-                           sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost);
+                           sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
     else if (fr->wave_cost)
         hipLaunchKernelGGL((sr_integrate_kernel<true, true>), dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream,
-                           sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost);
+                           sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
     else if (small && tr)  // the test-ray instantiations (the overlay visible)
         hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, true>),
                            dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps,
-                           ps_n, count, order, cost);
+                           ps_n, count, order, cost, start);
     else if (cull && general && tr)
         hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL, true>),
                            dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps,
-                           ps_n, count, order, cost);
+                           ps_n, count, order, cost, start);
     else if (cull && tr)
         hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, true>),
                            dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps,
-                           ps_n, count, order, cost);
+                           ps_n, count, order, cost, start);
     else if (small && fr->fast_unroll == 2)  // latency mode (sr_set_latency_mode)
         hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_SMALL, 2, SR_NC_SMALL>), dim3(slots * B * SR_WG_PER_TILE),
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost);
+                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
     else if (small)
         hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL>),
                            dim3(slots * B * SR_WG_PER_TILE),
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost);
+                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
     else if (cull && general)
         hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>),
                            dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc,
-                           tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost);
+                           tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
     else if (cull)
         hipLaunchKernelGGL(sr_integrate_kernel<true>, dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc,
-                           tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost);
+                           tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
     else  // the reference's loop (no budgets: the smallest LDS layout)
         hipLaunchKernelGGL((sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1>), dim3(slots * B * SR_WG_PER_TILE),
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost);
+                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
     if (ev4) (void)hipEventRecord(ev4[1], stream);
     OrderArgs oa{cost, order, (int)nblocks, fr->max_steps, split, split ? fr->split_log2 : 6, fr->split_min_steps};
     hipLaunchKernelGGL(sr_shade_kernel, dim3(grid.x, grid.y * B + (order ? 1u : 0u)), block, 0, stream, sc, segs, bg,

@@ -31,7 +31,7 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
                                          const sr_dev_frame* fr,
                                          uint8_t* out, size_t pitch, float* dbg_rgba, int32_t* dbg_steps,
                                          float* ps, size_t ps_n, int* list, int* count, int* order, int* cost,
-                                         int* diag, hipEvent_t* ev4, hipStream_t stream);
+                                         int* diag, sr_dev_start* start, hipEvent_t* ev4, hipStream_t stream);
 
 namespace {
 
@@ -116,6 +116,10 @@ struct sr_ctx {
     int64_t free_errors = 0;
     // device counter of the shade kernel's invariant check (sr_diag_counters)
     int* d_diag = nullptr;
+    // the start table: one record per frame of a batch, rebuilt by every
+    // launch on its stream before the integrate kernel reads it (geodesic.hip
+    // sr_start_table_kernel); nothing in it outlives the launch
+    sr_dev_start* d_start = nullptr;
     // optional per-kernel timing: 4 events per frame (before integrate, after
     // integrate, after shade, after resume), a ring of `timing_cap` frames
     std::vector<hipEvent_t> tev;
@@ -1016,7 +1020,7 @@ int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* pa
     }
     hipError_t e = sr_launch_geodesic(ctx->d_scene, tbl, ctx->d_segs, ctx->d_bg, ctx->d_arr, ctx->d_opq, &fr, out, pitch,
                                       dbg_rgba, dbg_steps, ctx->d_ps, ctx->ps_n, ctx->d_list, ctx->d_count, order, cost,
-                                      ctx->d_diag,
+                                      ctx->d_diag, ctx->d_start,
                                       ctx->timing_n < ctx->timing_cap ? &ctx->tev[4 * (size_t)ctx->timing_n++] : nullptr,
                                       s);
     if (hip_ok(e)) e = hipEventRecord(ctx->order_ev, s);
@@ -1091,12 +1095,14 @@ int sr_create(sr_ctx** out, int hip_device) {
     }
     if (!hip_ok(hipMalloc(&c->d_scene, sizeof(sr_dev_scene))) ||
         !hip_ok(hipMalloc(&c->d_segs, (size_t)SR_SEGS_BUF_FLOATS * sizeof(float))) ||
-        !hip_ok(hipMalloc(reinterpret_cast<void**>(&c->d_diag), sizeof(int)))) {
+        !hip_ok(hipMalloc(reinterpret_cast<void**>(&c->d_diag), sizeof(int))) ||
+        !hip_ok(hipMalloc(reinterpret_cast<void**>(&c->d_start), SR_MAX_BATCH * sizeof(sr_dev_start)))) {
         sr_destroy(c);
         return SR_E_NOMEM;
     }
     if (!hip_ok(hipMemsetAsync(c->d_scene, 0, sizeof(sr_dev_scene), c->upload)) ||
         !hip_ok(hipMemsetAsync(c->d_diag, 0, sizeof(int), c->upload)) ||
+        !hip_ok(hipMemsetAsync(c->d_start, 0, SR_MAX_BATCH * sizeof(sr_dev_start), c->upload)) ||
         !hip_ok(hipMemsetAsync(c->d_segs, 0, (size_t)SR_SEGS_BUF_FLOATS * sizeof(float),
                                c->upload)) ||
         !hip_ok(hipStreamSynchronize(c->upload))) {
@@ -1121,6 +1127,7 @@ void sr_destroy(sr_ctx* c) {
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->d_segs) (void)hipFree(c->d_segs);
     if (c->d_diag) (void)hipFree(c->d_diag);
+    if (c->d_start) (void)hipFree(c->d_start);
     // the rest came from the stream-ordered allocator: freed the same way,
     // then waited for (the context's frames are done: wait_ctx)
     const hipStream_t s = c->upload;
