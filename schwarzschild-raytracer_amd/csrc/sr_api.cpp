@@ -1270,12 +1270,20 @@ static void pack_slot(const sr_dev_obj& o, int cyl, sr_dev_slot& sl) {
     sl.rf = far_reach(o, sl.cn);
     switch (o.type) {
     case SR_OBJECT_RECTANGLE:
-    case SR_OBJECT_HOLLOW_DISK:
         sl.x0 = f[17];
         sl.x1 = f[18];
         break;
+    // disk_test and hollow_disk_test square their radii (o.f keeps them as
+    // given), so a negative radius accepts what its magnitude does; the
+    // clearance's radial distance rho - radius (geodesic.hip clearance_obj)
+    // needs the magnitude: the signed one put a disk of radius -R up to 2 R
+    // further away than it is, and rays went through it untested
+    case SR_OBJECT_HOLLOW_DISK:
+        sl.x0 = std::fabs(f[17]);
+        sl.x1 = std::fabs(f[18]);
+        break;
     case SR_OBJECT_DISK:
-        sl.x0 = f[17];
+        sl.x0 = std::fabs(f[17]);
         break;
     case SR_OBJECT_BOX:
         sl.x0 = f[12];
