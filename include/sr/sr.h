@@ -361,6 +361,65 @@ int sr_assemble_blocks(const uint8_t* stacked, size_t rank_stride, size_t in_fra
                        int world, int per, int height, int block_rows, size_t row_bytes, uint8_t* out,
                        size_t out_frame_stride, int n_frames, int on_device, sr_stream stream);
 
+/* ---- Supersampling (not in the reference, whose shader takes one sample at
+ * each pixel centre): an ordered grid of ss x ss samples per pixel, ss in
+ * 1 .. SR_MAX_SUPERSAMPLE, with a box resolve. The sample frame S is exactly
+ * the frame this library renders for (ss * width) x (ss * height) with the
+ * same scene, camera (the fov is horizontal, so the framing is the same),
+ * params, textures and test ray. Output pixel (x, y), channel c:
+ *
+ *   out[y][x][c] = (sum_{j < ss} sum_{i < ss} S[ss*y + j][ss*x + i][c] + (ss*ss) / 2) div (ss*ss)
+ *
+ * in integers on S's RGBA8 bytes ((ss*ss) / 2 = 0, 2, 4, 8), all four
+ * channels alike. The sum does not depend on its order, so every
+ * implementation of the rule gives the same bits. By that definition:
+ *  - the crosshair (params.crosshair) is drawn in the sample frame and comes
+ *    out 1 / ss the size (a caller who wants a fixed size draws their own);
+ *  - the noise mask (percent_black) and the split modes (raytrace_type) are
+ *    evaluated per sample;
+ *  - ss == 1 is the plain frame, byte for byte (no scratch, no resolve).
+ * sr_set_split, sr_set_latency_mode and the learned launch order apply to the
+ * sample frame as to any frame of its size.
+ *
+ * Scratch: a context keeps one sample buffer, grown on demand in stream order
+ * on the launch's stream and released by sr_destroy, of
+ *   4 * ss*ss * width * rows * n_frames bytes
+ * for the largest launch so far (rows: the output rows of the call's tile;
+ * 33 MB for one 1920x1080 frame at ss 2, 4.2 GB for 32 of them at ss 4).
+ * SR_E_NOMEM, with nothing launched, when it cannot be allocated. The resolve
+ * runs on the same stream after the sample launch. */
+#define SR_MAX_SUPERSAMPLE 4
+
+/* sr_render with supersampling: rows [row_begin, row_end) of the width x
+ * height output frame, each pixel from ss x ss samples. SR_E_INVALID for ss
+ * outside 1 .. SR_MAX_SUPERSAMPLE, or more than 2^24 sample rows. */
+int sr_render_ss(sr_ctx* ctx, const sr_camera* cam, const sr_params* params, int width, int height,
+                 int row_begin, int row_end, int ss, uint8_t* dev_rgba8, size_t pitch_bytes,
+                 sr_stream stream);
+
+/* sr_render_block_list with supersampling: the same layout (n_frames cameras,
+ * an explicit block list, -1 padding and the rows past the frame's last row
+ * left unwritten), width, height, block_rows, pitch and frame stride all
+ * those of the OUTPUT frame, so a rank's tile has the shape
+ * sr_assemble_blocks expects. SR_E_INVALID when ss * n_blocks * block_rows
+ * exceeds 2^24 rows. dist.supersample_block_costs prices the output blocks
+ * from an sr_wave_costs map of the sample frame. */
+int sr_render_block_list_ss(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* params,
+                            int width, int height, int block_rows, const int* blocks, int n_blocks,
+                            int ss, uint8_t* dev_rgba8, size_t pitch_bytes,
+                            size_t frame_stride_bytes, sr_stream stream);
+
+/* The resolve alone: n_frames sample images of (ss * width) x (ss * rows)
+ * (row r at samples + f * sample_frame_stride + r * sample_pitch) to width x
+ * rows images by the rule above. on_device != 0: device pointers, a kernel
+ * on `stream`, asynchronous (vector loads when the sample pointer, pitch and
+ * stride are multiples of 8 / 4 / 16 bytes for ss 2 / 3 / 4 and the output's
+ * of 4, a byte path otherwise); 0: host memory, synchronous (the same rule
+ * in plain C++). */
+int sr_resolve_box(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride,
+                   int width, int rows, int ss, uint8_t* out, size_t pitch, size_t out_frame_stride,
+                   int n_frames, int on_device, sr_stream stream);
+
 /* Debug/parity variant: unclamped FragColor as float RGBA (dev_rgba32, may be
  * NULL), the RGBA8 pixel (dev_rgba8, may be NULL) and the number of executed
  * geodesic steps per pixel (dev_steps, may be NULL). Dense rows. */

@@ -203,7 +203,12 @@ SIGNATURES = {
     "sr_balanced_blocks": (_i, [_p, _i, _i, _p, _i, C.POINTER(_i)]),
     "sr_assemble_blocks": (_i, [_p, C.c_size_t, C.c_size_t, _p, _i, _i, _i, _i, C.c_size_t, _p, C.c_size_t, _i, _i,
                                 _p]),
+    "sr_render_ss": (_i, [_p, C.POINTER(Camera), C.POINTER(Params), _i, _i, _i, _i, _i, _p, C.c_size_t, _p]),
+    "sr_render_block_list_ss": (_i, [_p, C.POINTER(Camera), _i, C.POINTER(Params), _i, _i, _i, C.POINTER(_i), _i, _i,
+                                     _p, C.c_size_t, C.c_size_t, _p]),
+    "sr_resolve_box": (_i, [_p, C.c_size_t, C.c_size_t, _i, _i, _i, _p, C.c_size_t, C.c_size_t, _i, _i, _p]),
 }
+MAX_SUPERSAMPLE = 4
 # exported beside the header set (parity tooling)
 EXTRA_SIGNATURES = {
     "sr_debug_set_culling": (_i, [_p, _i]),
@@ -268,6 +273,23 @@ def write_png(path, frame, flip_rows: bool = True) -> None:
         raise ValueError(f"expected an [H, W, 4] frame, got {a.shape}")
     h, w, _ = a.shape
     check(load().sr_write_png(str(path).encode(), a.ctypes.data, w, h, w * 4, 1 if flip_rows else 0), "sr_write_png")
+
+
+def resolve_box(samples, ss: int):
+    """sr_resolve_box's host form: uint8 sample frames [..., ss * rows, ss * W, 4]
+    (host array) -> their box-resolved [..., rows, W, 4]."""
+    import numpy as np
+
+    a = np.ascontiguousarray(samples, dtype=np.uint8)
+    if a.ndim < 3 or a.shape[-1] != 4 or ss < 1 or a.shape[-3] % ss or a.shape[-2] % ss:
+        raise ValueError(f"expected [..., {ss} * rows, {ss} * W, 4] samples, got {a.shape}")
+    lead, rows, w = a.shape[:-3], a.shape[-3] // ss, a.shape[-2] // ss
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    out = np.empty(lead + (rows, w, 4), dtype=np.uint8)
+    if n and rows and w:
+        check(load().sr_resolve_box(a.ctypes.data, 4 * ss * w, 4 * ss * w * ss * rows, w, rows, ss, out.ctypes.data,
+                                    4 * w, 4 * w * rows, n, 0, None), "sr_resolve_box")
+    return out
 
 
 def check_layout() -> dict:

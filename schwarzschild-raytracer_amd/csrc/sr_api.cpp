@@ -120,6 +120,10 @@ struct sr_ctx {
     // launch on its stream before the integrate kernel reads it (geodesic.hip
     // sr_start_table_kernel); nothing in it outlives the launch
     sr_dev_start* d_start = nullptr;
+    // the sample frame of a supersampled launch (sr_render_ss,
+    // sr_render_block_list_ss; resolve.hip reads it): grown on demand, reused
+    uint8_t* d_ss = nullptr;
+    size_t ss_bytes = 0;
     // optional per-kernel timing: 4 events per frame (before integrate, after
     // integrate, after shade, after resume), a ring of `timing_cap` frames
     std::vector<hipEvent_t> tev;
@@ -659,6 +663,20 @@ int ensure_pixel_state(sr_ctx* ctx, size_t n, hipStream_t s) {
     return SR_OK;
 }
 
+// Grows the sample scratch of the supersampled launches the same way.
+int ensure_sample_scratch(sr_ctx* ctx, size_t bytes, hipStream_t s) {
+    if (bytes <= ctx->ss_bytes) return SR_OK;
+    release(ctx, ctx->d_ss, s);
+    ctx->d_ss = nullptr;
+    ctx->ss_bytes = 0;
+    if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&ctx->d_ss), bytes, s))) {
+        ctx->d_ss = nullptr;
+        return SR_E_NOMEM;
+    }
+    ctx->ss_bytes = bytes;
+    return SR_OK;
+}
+
 // Opacity bitmap of the texture array for the step loop's hit classification
 // (geodesic.hip hit_opacity): bit (layer, y, x) is set when every texel within
 // +-SR_OPQ_RADIUS of (x, y), wrapping like the sampler, has alpha 255. A
@@ -944,6 +962,21 @@ int build_frame(sr_ctx* ctx, const sr_camera* cam, const sr_params* p, int width
     return SR_OK;
 }
 
+// Makes `s` the context's launch stream: ordered after the launches on the
+// previous one, and the target of every stream-ordered free from here on
+// (ensure_*'s evictions).
+int enter_stream(sr_ctx* ctx, hipStream_t s) {
+    if (!hip_ok(hipSetDevice(ctx->device))) return SR_E_HIP;
+    if (ctx->launched && s != ctx->last_stream) {
+        // order_ev was recorded at the end of the last launch, so the old
+        // stream's handle is not touched here (the caller may have destroyed
+        // it since)
+        if (!hip_ok(hipStreamWaitEvent(s, ctx->order_ev, 0))) return SR_E_HIP;
+    }
+    ctx->last_stream = s;
+    return SR_OK;
+}
+
 // Renders the same rows of n_frames frames (cams[f]; output f at out + f *
 // frame_stride) in one launch of each kernel.
 int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* params, int width, int height,
@@ -994,16 +1027,9 @@ int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* pa
     fr.block_stride = block_stride;
     fr.block_list = d_block_list;
     fr.wave_cost = d_wave_cost;
-    if (!hip_ok(hipSetDevice(ctx->device))) return SR_E_HIP;
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (ctx->launched && s != ctx->last_stream) {
-        // ordered after the launches on the previous stream: order_ev was
-        // recorded at the end of the last launch, so the old stream's handle
-        // is not touched here (the caller may have destroyed it since)
-        if (!hip_ok(hipStreamWaitEvent(s, ctx->order_ev, 0))) return SR_E_HIP;
-    }
-    // every stream-ordered free from here on (ensure_*'s evictions) goes to s
-    ctx->last_stream = s;
+    rc = enter_stream(ctx, s);
+    if (rc != SR_OK) return rc;
     const float4* tbl = nullptr;
     rc = ensure_table(ctx, params->max_steps, params->max_revolutions, s, &tbl);
     if (rc != SR_OK) return rc;
@@ -1037,6 +1063,15 @@ extern "C" hipError_t sr_assemble_blocks_device(const uint8_t* stacked, size_t r
 extern "C" int sr_assemble_blocks_host(const uint8_t* stacked, size_t rank_stride, size_t in_frame_stride,
                                        const int* lists, int world, int per, int height, int block_rows,
                                        size_t row_bytes, uint8_t* out, size_t out_frame_stride, int n_frames);
+
+// resolve.hip
+extern "C" hipError_t sr_resolve_box_device(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride,
+                                            int width, int rows, int ss, const int* dev_blocks, int block_rows,
+                                            int height, uint8_t* out, size_t pitch, size_t out_frame_stride,
+                                            int n_frames, hipStream_t stream);
+extern "C" void sr_resolve_box_host(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride, int width,
+                                    int rows, int ss, uint8_t* out, size_t pitch, size_t out_frame_stride,
+                                    int n_frames);
 
 extern "C" {
 
@@ -1138,6 +1173,7 @@ void sr_destroy(sr_ctx* c) {
         release(c, c->d_opq, s);
         for (auto& kv : c->tables) release(c, kv.second.dev, s);
         free_pixel_state(c, s);
+        release(c, c->d_ss, s);
         for (auto& kv : c->orders) {
             release(c, kv.second.order, s);
             release(c, kv.second.cost, s);
@@ -1513,6 +1549,103 @@ int sr_render_blocks_batch(sr_ctx* c, const sr_camera* cams, int n_frames, const
     for (int b = block_first; b * block_rows < height; b += block_step) nblocks++;
     return launch(c, cams, n_frames, p, width, height, nblocks * block_rows, block_first * block_rows, block_rows,
                   block_step * block_rows, out, pitch, frame_stride, nullptr, nullptr, stream);
+}
+
+// ---- supersampling: the sample frame is an ordinary launch of the (ss x
+// width) x (ss x height) frame into the context's sample scratch, resolved
+// to the caller's buffer by resolve.hip on the same stream
+
+int sr_resolve_box(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride, int width, int rows, int ss,
+                   uint8_t* out, size_t pitch, size_t out_frame_stride, int n_frames, int on_device,
+                   sr_stream stream) {
+    if (ss < 1 || ss > SR_MAX_SUPERSAMPLE) return SR_E_INVALID;
+    if (!samples || !out || width <= 0 || rows < 0 || n_frames < 1) return SR_E_INVALID;
+    if (width > INT32_MAX / (4 * ss) || rows > (1 << 24) / ss) return SR_E_INVALID;
+    if (pitch < (size_t)width * 4 || sample_pitch < (size_t)width * 4 * (size_t)ss) return SR_E_INVALID;
+    if (n_frames > 1 &&
+        (out_frame_stride < pitch * (size_t)rows || sample_frame_stride < sample_pitch * (size_t)rows * (size_t)ss))
+        return SR_E_INVALID;
+    if (!on_device) {
+        sr_resolve_box_host(samples, sample_pitch, sample_frame_stride, width, rows, ss, out, pitch, out_frame_stride,
+                            n_frames);
+        return SR_OK;
+    }
+    const hipError_t e = sr_resolve_box_device(samples, sample_pitch, sample_frame_stride, width, rows, ss, nullptr, 0,
+                                               rows, out, pitch, out_frame_stride, n_frames,
+                                               reinterpret_cast<hipStream_t>(stream));
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
+}
+
+// The sample launch and its resolve. The tile has `rows` output rows per
+// frame (a block list's slots x block_rows, or one band of `rows` rows from
+// row_base); every argument was checked by the caller and check_frames.
+static int launch_ss(sr_ctx* c, const sr_camera* cams, int n_frames, const sr_params* p, int width, int height,
+                     int rows, int row_base, int block_rows, const int* d_blocks, int ss, uint8_t* out, size_t pitch,
+                     size_t frame_stride, sr_stream stream) {
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    const size_t spitch = (size_t)width * 4 * (size_t)ss;
+    const size_t sstride = spitch * (size_t)rows * (size_t)ss;
+    rc = ensure_sample_scratch(c, sstride * (size_t)n_frames, s);
+    if (rc != SR_OK) return rc;
+    rc = launch(c, cams, n_frames, p, ss * width, ss * height, ss * rows, ss * row_base, ss * block_rows,
+                d_blocks ? ss * block_rows : 0, c->d_ss, spitch, n_frames > 1 ? sstride : 0, nullptr, nullptr, stream,
+                d_blocks);
+    if (rc != SR_OK) return rc;
+    hipError_t e = sr_resolve_box_device(c->d_ss, spitch, sstride, width, rows, ss, d_blocks, block_rows, height, out,
+                                         pitch, frame_stride, n_frames, s);
+    // again at the end of the whole: a launch on another stream waits for the resolve too
+    if (hip_ok(e)) e = hipEventRecord(c->order_ev, s);
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
+}
+
+// launch()'s own rejections, ahead of the scratch allocation
+static int check_frames(sr_ctx* c, const sr_camera* cams, int n_frames, const sr_params* p, int width, int height) {
+    if (!c) return SR_E_INVALID;
+    if (!c->scene_set) return SR_E_NOT_READY;
+    if (!cams || n_frames < 1) return SR_E_INVALID;
+    if (n_frames > SR_MAX_BATCH) return SR_E_CAPACITY;
+    sr_dev_frame fr;
+    return build_frame(c, cams, p, width, height, fr);
+}
+
+int sr_render_ss(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int row_begin,
+                 int row_end, int ss, uint8_t* out, size_t pitch, sr_stream stream) {
+    if (ss < 1 || ss > SR_MAX_SUPERSAMPLE) return SR_E_INVALID;
+    if (ss == 1) return sr_render(c, cam, p, width, height, row_begin, row_end, out, pitch, stream);
+    if (!out || row_begin < 0 || row_end > height || row_begin > row_end) return SR_E_INVALID;
+    int rc = check_frames(c, cam, 1, p, width, height);
+    if (rc != SR_OK) return rc;
+    const int n = row_end - row_begin;
+    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss || n > (1 << 24) / ss)
+        return SR_E_INVALID;
+    if (n == 0) return SR_OK;  // no rows: nothing is written
+    return launch_ss(c, cam, 1, p, width, height, n, row_begin, n, nullptr, ss, out, pitch, 0, stream);
+}
+
+int sr_render_block_list_ss(sr_ctx* c, const sr_camera* cams, int n_frames, const sr_params* p, int width,
+                            int height, int block_rows, const int* blocks, int n_blocks, int ss, uint8_t* out,
+                            size_t pitch, size_t frame_stride, sr_stream stream) {
+    if (ss < 1 || ss > SR_MAX_SUPERSAMPLE) return SR_E_INVALID;
+    if (ss == 1)
+        return sr_render_block_list(c, cams, n_frames, p, width, height, block_rows, blocks, n_blocks, out, pitch,
+                                    frame_stride, stream);
+    if (!c || !out || !blocks || block_rows <= 0 || n_blocks <= 0 || height <= 0) return SR_E_INVALID;
+    if ((long long)ss * n_blocks * block_rows > (1 << 24)) return SR_E_INVALID;
+    const int nb = (height + block_rows - 1) / block_rows;
+    for (int i = 0; i < n_blocks; i++)
+        if (blocks[i] < -1 || blocks[i] >= nb) return SR_E_INVALID;
+    int rc = check_frames(c, cams, n_frames, p, width, height);
+    if (rc != SR_OK) return rc;
+    const int rows = n_blocks * block_rows;
+    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss) return SR_E_INVALID;
+    if (n_frames > 1 && frame_stride < pitch * (size_t)rows) return SR_E_INVALID;
+    if (!hip_ok(hipSetDevice(c->device))) return SR_E_HIP;
+    const int* d = nullptr;
+    rc = ensure_block_list(c, blocks, n_blocks, reinterpret_cast<hipStream_t>(stream), &d);
+    if (rc != SR_OK) return rc;
+    return launch_ss(c, cams, n_frames, p, width, height, rows, 0, block_rows, d, ss, out, pitch, frame_stride, stream);
 }
 
 int sr_render_debug(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int row_begin,

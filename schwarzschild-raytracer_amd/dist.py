@@ -87,6 +87,25 @@ def block_costs(wave_cost, event_steps: float = EVENT_STEPS):
     return out
 
 
+def supersample_block_costs(sample_costs, ss: int, height: int, block_rows: int = 8):
+    """Per-block cost of a supersampled frame (sr_render_block_list_ss) of
+    `height` output rows: output block b covers the sample frame's rows
+    [ss * b * block_rows, ss * (b + 1) * block_rows), i.e. with 8-row blocks
+    its 8-row blocks ss * b .. ss * b + ss - 1 (clipped at the sample frame's
+    block count), and costs their sum. sample_costs: block_costs of an
+    sr_wave_costs map rendered at the sample size (ss * width) x (ss * height).
+    block_rows: a multiple of 8. -> float64 [nblocks(height, block_rows)]."""
+    c = np.asarray(sample_costs, dtype=np.float64)
+    if ss < 1 or block_rows <= 0 or block_rows % 8:
+        raise ValueError(f"ss {ss}, block_rows {block_rows}: ss >= 1 and 8-row sample blocks are needed")
+    ns = nblocks(ss * height, 8)
+    if c.shape != (ns,):
+        raise ValueError(f"expected the {ns} 8-row block costs of the sample frame, got {c.shape}")
+    k = ss * (block_rows // 8)  # sample blocks per output block
+    return np.array([c[b * k:min(ns, (b + 1) * k)].sum() for b in range(nblocks(height, block_rows))],
+                    dtype=np.float64)
+
+
 def balanced_blocks(costs, world: int) -> list[list[int]]:
     """balanced_blocks_py through the C-ABI (sr_balanced_blocks,
     csrc/host/partition.cpp): the same lists, computed by the library."""

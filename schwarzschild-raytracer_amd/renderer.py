@@ -183,6 +183,44 @@ class Renderer:
         )
         return out
 
+    def render_ss(self, cam: abi.Camera, params: abi.Params, width: int, height: int, ss: int, row_begin: int = 0,
+                  row_end: int | None = None, out=None, stream=None):
+        """render with ss x ss samples per pixel and a box resolve
+        (sr_render_ss; ss 1 .. abi.MAX_SUPERSAMPLE, 1: the plain frame):
+        rows [row_begin, row_end) of the width x height frame -> [rows, width, 4]."""
+        row_end = height if row_end is None else row_end
+        rows = row_end - row_begin
+        if out is None:
+            out = self.torch.empty((max(rows, 0), width, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and out.numel() >= rows * width * 4
+        abi.check(
+            self.lib.sr_render_ss(self.ctx, C.byref(cam), C.byref(params), width, height, row_begin, row_end, int(ss),
+                                  C.c_void_p(out.data_ptr()), width * 4, self._stream(stream)),
+            "sr_render_ss",
+        )
+        return out
+
+    def render_block_list_ss(self, cams, params: abi.Params, width: int, height: int, block_rows: int, blocks,
+                             ss: int, out=None, stream=None):
+        """render_block_list with ss x ss samples per pixel (sr_render_block_list_ss):
+        sizes and block_rows in output pixels -> [B, len(blocks) * block_rows, W, 4]."""
+        blocks = [int(b) for b in blocks]
+        B = len(cams)
+        arr = (abi.Camera * B)(*cams)
+        lst = (C.c_int * len(blocks))(*blocks)
+        rows = len(blocks) * block_rows
+        if out is None:
+            out = self.torch.empty((B, rows, width, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and tuple(out.shape[:1]) == (B,)
+        assert out[0].numel() >= rows * width * 4
+        abi.check(
+            self.lib.sr_render_block_list_ss(self.ctx, arr, B, C.byref(params), width, height, block_rows, lst,
+                                             len(blocks), int(ss), C.c_void_p(out.data_ptr()), width * 4,
+                                             out[0].numel(), self._stream(stream)),
+            "sr_render_block_list_ss",
+        )
+        return out
+
     def render_debug(self, cam: abi.Camera, params: abi.Params, width: int, height: int, row_begin: int = 0,
                      row_end: int | None = None, stream=None):
         """(float RGBA FragColor, RGBA8, executed steps) for rows [row_begin, row_end)."""

@@ -6,6 +6,7 @@ hyperbolic trajectory (src/main.cpp:404-410) in batched launches.
 
   python tools/render.py --out frame.png [--width 1920 --height 1080 --max-steps 2000]
   python tools/render.py --flyby 8 --out flyby_%02d.png
+  python tools/render.py --ssaa 2 --out frame_ss2.png      (2 x 2 samples per pixel, box resolve)
 """
 import argparse
 import sys
@@ -28,6 +29,8 @@ def main():
     ap.add_argument("--crosshair", action="store_true")
     ap.add_argument("--textures", choices=["assets", "standin"], default="assets")
     ap.add_argument("--flyby", type=int, default=0, help="frames along the hyperbolic flyby (0: the default camera)")
+    ap.add_argument("--ssaa", type=int, default=1, choices=[1, 2, 3, 4],
+                    help="supersampling: N x N samples per pixel, box resolve (sr_render_ss; 1: off)")
     args = ap.parse_args()
     import torch
 
@@ -49,15 +52,18 @@ def main():
     params.crosshair = 1 if args.crosshair else 0
     W, H = args.width, args.height
     if args.flyby <= 0:
-        frame = r.render(abi.default_camera(), params, W, H)
+        frame = r.render_ss(abi.default_camera(), params, W, H, args.ssaa)
         torch.cuda.synchronize()
         abi.write_png(args.out, frame.cpu().numpy())
         print(f"wrote {args.out}")
     else:
         n = args.flyby
         cams = [abi.camera_flyby((f + 0.5) / n, 30.0, 10.0) for f in range(n)]
-        for first in range(0, n, 32):  # sr_render_blocks_batch takes up to 32 frames
-            out, rows = r.render_blocks_batch(cams[first:first + 32], params, W, H, H, 0, 1)
+        # up to 32 frames per launch, fewer while the sample scratch of a batch
+        # (4 ssaa^2 W H bytes per frame) would pass 2 GiB
+        per = max(1, min(32, (2 << 30) // (4 * args.ssaa ** 2 * W * H)))
+        for first in range(0, n, per):  # one block of H rows: the whole frame
+            out, rows = r.render_block_list_ss(cams[first:first + per], params, W, H, H, [0], args.ssaa), H
             torch.cuda.synchronize()
             for k, fr in enumerate(out.cpu().numpy()):
                 path = args.out % (first + k) if "%" in args.out else f"{Path(args.out).stem}_{first + k:03d}.png"
