@@ -420,6 +420,69 @@ int sr_resolve_box(const uint8_t* samples, size_t sample_pitch, size_t sample_fr
                    int width, int rows, int ss, uint8_t* out, size_t pitch, size_t out_frame_stride,
                    int n_frames, int on_device, sr_stream stream);
 
+/* ---- Adaptive supersampling (not in the reference): supersample only the
+ * 16x16 output tiles of the frame that hold an edge. Inputs: one camera and
+ * one whole width x height frame, ss in 2 .. SR_MAX_SUPERSAMPLE, threshold
+ * (int), grow in 0 .. 2. Byte-exact, no tolerance anywhere:
+ *
+ *  - P is the plain width x height frame, exactly what sr_render writes; S the
+ *    (ss * width) x (ss * height) sample frame exactly as sr_render_ss defines
+ *    it; R is S's box resolve by the rule above.
+ *  - Output tile (tx, ty) covers pixels x in [16 tx, 16 tx + 15] and y in
+ *    [16 ty, 16 ty + 15], clipped to the frame: ceil(width / 16) x
+ *    ceil(height / 16) tiles. An output tile is exactly the ss x ss block
+ *    (ss tx + i, ss ty + j) of the sample frame's own 16x16 workgroup tiles,
+ *    for every ss (the ones past the sample grid's edge on a partial tile do
+ *    not exist).
+ *  - Edge rule, on P's RGBA8 bytes, all four channels alike: two pixels that
+ *    are horizontal or vertical neighbours inside the frame form an edge pair
+ *    when max over c of |a_c - b_c| > threshold. A tile is seeded when a pixel
+ *    of it belongs to an edge pair; a pair that straddles a tile boundary
+ *    seeds both tiles. threshold < 0 seeds every tile, threshold >= 255 none.
+ *  - The flagged set is the seeded set dilated `grow` times by the 3x3
+ *    (Chebyshev) neighbourhood on the tile grid.
+ *  - out[y][x] = R[y][x] when pixel (x, y)'s tile is flagged, else P[y][x].
+ *
+ * By that definition:
+ *  - the crosshair, the noise mask (percent_black) and the split modes
+ *    (raytrace_type) follow P in an unflagged tile and S in a flagged one; a
+ *    noise mask therefore flags nearly everything;
+ *  - a feature thinner than a pixel that P misses entirely is not found:
+ *    `grow` is the knob for that;
+ *  - with threshold < 0 the output equals sr_render_ss's, byte for byte;
+ *  - with threshold >= 255 it equals sr_render's, and no sample work is
+ *    launched.
+ *
+ * sr_render_adaptive renders P into dev_rgba8 with the ordinary launch (which
+ * runs and learns the launch order as sr_render does), selects the tiles
+ * with a kernel, launches the sample frame for the flagged tiles only and
+ * resolves them over P, all asynchronous on `stream` with no host
+ * synchronisation anywhere in the call. sr_set_latency_mode and culling apply
+ * to the sample launch; sr_set_split does not, and no launch order is learned
+ * from it or for it (its tiles run in the order the plain frame just learned,
+ * costliest first). Whole frames only, one camera: row bands, block
+ * lists, batches and the multi-GPU path are out of scope. dev_tile_mask (may
+ * be NULL; device memory, [ceil(height / 16)][ceil(width / 16)] bytes 0 / 1)
+ * receives the flagged set. Scratch: the sample buffer and the pixel state of
+ * the whole sample frame, as for sr_render_ss of the frame (4 and 208 bytes
+ * per sample), and 1 + 4 ss^2 bytes per tile; all kept by the context, grown
+ * in stream order, released by sr_destroy. SR_E_INVALID for ss outside
+ * 2 .. SR_MAX_SUPERSAMPLE, grow outside 0 .. 2, a null output, pitch_bytes <
+ * 4 * width, or more than 2^24 sample rows; SR_E_NOT_READY and SR_E_NOMEM
+ * (nothing launched) as for sr_render_ss. */
+int sr_render_adaptive(sr_ctx* ctx, const sr_camera* cam, const sr_params* params, int width, int height,
+                       int ss, int threshold, int grow, uint8_t* dev_rgba8, size_t pitch_bytes,
+                       uint8_t* dev_tile_mask, sr_stream stream);
+
+/* The selection alone: the flagged set of a width x height RGBA8 image (row y
+ * at rgba8 + y * pitch) by the edge rule and `grow` above into
+ * tile_mask[ceil(height / 16)][ceil(width / 16)], bytes 0 / 1. on_device !=
+ * 0: device pointers, kernels on `stream`, asynchronous; 0: host memory,
+ * synchronous (the same rule in plain C++). SR_E_INVALID for null pointers,
+ * sizes <= 0, pitch < 4 * width or grow outside 0 .. 2. */
+int sr_edge_tiles(const uint8_t* rgba8, size_t pitch, int width, int height, int threshold, int grow,
+                  uint8_t* tile_mask, int on_device, sr_stream stream);
+
 /* Debug/parity variant: unclamped FragColor as float RGBA (dev_rgba32, may be
  * NULL), the RGBA8 pixel (dev_rgba8, may be NULL) and the number of executed
  * geodesic steps per pixel (dev_steps, may be NULL). Dense rows. */

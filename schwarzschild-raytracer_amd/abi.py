@@ -207,6 +207,8 @@ SIGNATURES = {
     "sr_render_block_list_ss": (_i, [_p, C.POINTER(Camera), _i, C.POINTER(Params), _i, _i, _i, C.POINTER(_i), _i, _i,
                                      _p, C.c_size_t, C.c_size_t, _p]),
     "sr_resolve_box": (_i, [_p, C.c_size_t, C.c_size_t, _i, _i, _i, _p, C.c_size_t, C.c_size_t, _i, _i, _p]),
+    "sr_render_adaptive": (_i, [_p, C.POINTER(Camera), C.POINTER(Params), _i, _i, _i, _i, _i, _p, C.c_size_t, _p, _p]),
+    "sr_edge_tiles": (_i, [_p, C.c_size_t, _i, _i, _i, _i, _p, _i, _p]),
 }
 MAX_SUPERSAMPLE = 4
 # exported beside the header set (parity tooling)
@@ -289,6 +291,23 @@ def resolve_box(samples, ss: int):
     if n and rows and w:
         check(load().sr_resolve_box(a.ctypes.data, 4 * ss * w, 4 * ss * w * ss * rows, w, rows, ss, out.ctypes.data,
                                     4 * w, 4 * w * rows, n, 0, None), "sr_resolve_box")
+    return out
+
+
+def edge_tiles(frame, threshold: int, grow: int = 0):
+    """sr_edge_tiles' host form: an [H, W, 4] uint8 frame (host array, rows may
+    be strided) -> its flagged 16x16 tiles, uint8 [ceil(H / 16), ceil(W / 16)]."""
+    import numpy as np
+
+    a = np.asarray(frame)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4 or a.strides[1:] != (4, 1) or a.strides[0] < 0:
+        a = np.ascontiguousarray(frame, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"expected an [H, W, 4] frame, got {a.shape}")
+    h, w, _ = a.shape
+    out = np.empty(((h + 15) // 16, (w + 15) // 16), dtype=np.uint8)
+    check(load().sr_edge_tiles(a.ctypes.data, a.strides[0], w, h, int(threshold), int(grow), out.ctypes.data, 0, None),
+          "sr_edge_tiles")
     return out
 
 

@@ -3277,6 +3277,9 @@ struct OrderArgs {
 #ifndef SR_SHADE_WAVES_PER_EU
 #define SR_SHADE_WAVES_PER_EU 1
 #endif
+// SPARSE: the sparse launch's instantiation (`codes`, sr_launch_geodesic); every
+// other launch runs <false>, whose code has no trace of the list
+template <bool SPARSE>
 __global__ __launch_bounds__(256, SR_SHADE_WAVES_PER_EU) void sr_shade_kernel(const sr_dev_scene* __restrict__ sc,
                                                       const float* __restrict__ segs,
                                                       const uint32_t* __restrict__ bg,
@@ -3285,7 +3288,8 @@ __global__ __launch_bounds__(256, SR_SHADE_WAVES_PER_EU) void sr_shade_kernel(co
                                                       uint8_t* __restrict__ out, size_t pitch,
                                                       float* __restrict__ dbg_rgba, int32_t* __restrict__ dbg_steps,
                                                       int* __restrict__ list, int* __restrict__ count,
-                                                      int* __restrict__ diag, OrderArgs oa) {
+                                                      int* __restrict__ diag, OrderArgs oa,
+                                                      const int* __restrict__ codes) {
     // with a launch order to compute, grid row 0 is its workgroup's (block
     // (0, 0)) and the frames' tiles follow in rows 1 ..
     const int row0 = oa.order ? 1 : 0;
@@ -3294,7 +3298,12 @@ __global__ __launch_bounds__(256, SR_SHADE_WAVES_PER_EU) void sr_shade_kernel(co
             order_tiles(oa.cost, oa.n, oa.max_cost, oa.order, oa.split_tiles, oa.split_log2, oa.split_min);
         return;
     }
-    const int vblock = ((int)blockIdx.y - row0) * gridDim.x + blockIdx.x;  // frame f's tiles are rows f*gy ..
+    int vblock = ((int)blockIdx.y - row0) * gridDim.x + blockIdx.x;  // frame f's tiles are rows f*gy ..
+    if constexpr (SPARSE) {  // one frame: workgroup i shades the tile of the integrate kernel's code i
+        const int code = codes[vblock];
+        if (code < 0) return;
+        vblock = code >> 8;
+    }
     const int f = vblock / fr.tiles, block = vblock - f * fr.tiles;
     Pix q;
     if (!pixel_of(fr, block, threadIdx.x, q)) return;
@@ -3416,7 +3425,11 @@ __global__ __launch_bounds__(SR_WG) void sr_resume_kernel(const sr_dev_scene* __
 }
 
 // order/cost (optional, one int per workgroup tile): the launch order and
-// the cost feedback of order_tiles
+// the cost feedback of order_tiles. order without cost is a sparse launch
+// (sr_render_adaptive): one frame, `order` a caller-made list of whole-tile
+// codes with -1 behind them, one entry per tile of the grid. Only the listed
+// tiles are integrated and shaded, no cost is recorded and no order is
+// computed (order_tiles does not run), split tiles do not apply.
 extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* tbl, const float* segs,
                                          const uint32_t* bg, const uint32_t* arr, const uint8_t* opq,
                                          const sr_dev_frame* fr, uint8_t* out, size_t pitch, float* dbg_rgba,
@@ -3430,9 +3443,11 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
     const unsigned B = (unsigned)fr->batch;
     if (B < 1 || B > SR_MAX_BATCH || fr->tiles != (int)nblocks) return hipErrorInvalidValue;
     if ((size_t)nblocks * B * 256 > ps_n || (size_t)nblocks * B * 256 > (size_t)INT32_MAX) return hipErrorInvalidValue;
-    if ((order == nullptr) != (cost == nullptr)) return hipErrorInvalidValue;
+    if (cost != nullptr && order == nullptr) return hipErrorInvalidValue;
+    const bool sparse = order != nullptr && cost == nullptr;
+    if (sparse && (B != 1 || fr->wave_cost)) return hipErrorInvalidValue;
     // split tiles need the launch order (their codes come from order_tiles)
-    const int split = order ? fr->split_tiles : 0;
+    const int split = order && !sparse ? fr->split_tiles : 0;
     if (split < 0 || (split && (fr->split_log2 < 0 || fr->split_log2 > 4 || (fr->split_log2 & 1))))
         return hipErrorInvalidValue;
     if (nblocks > (1u << 22)) return hipErrorInvalidValue;  // tile << 8 stays a positive int
@@ -3488,9 +3503,14 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
         hipLaunchKernelGGL((sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1>), dim3(slots * B * SR_WG_PER_TILE),
                            dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
     if (ev4) (void)hipEventRecord(ev4[1], stream);
-    OrderArgs oa{cost, order, (int)nblocks, fr->max_steps, split, split ? fr->split_log2 : 6, fr->split_min_steps};
-    hipLaunchKernelGGL(sr_shade_kernel, dim3(grid.x, grid.y * B + (order ? 1u : 0u)), block, 0, stream, sc, segs, bg,
-                       arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa);
+    OrderArgs oa{cost, sparse ? nullptr : order, (int)nblocks, fr->max_steps, split, split ? fr->split_log2 : 6, fr->split_min_steps};
+    if (sparse)
+        hipLaunchKernelGGL(sr_shade_kernel<true>, dim3(grid.x, grid.y), block, 0, stream, sc, segs, bg, arr, *fr, ps, ps_n,
+                           out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa, (const int*)order);
+    else
+        hipLaunchKernelGGL(sr_shade_kernel<false>, dim3(grid.x, grid.y * B + (order ? 1u : 0u)), block, 0, stream, sc,
+                           segs, bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa,
+                           (const int*)nullptr);
     if (ev4) (void)hipEventRecord(ev4[2], stream);
 #ifndef SR_RESUME_TILES  // the resume kernel's grid-stride grid, in 256-thread tiles
 #define SR_RESUME_TILES 1024u

@@ -38,24 +38,12 @@ __device__ __forceinline__ uint32_t box_average(uint32_t even, uint32_t odd) {
     return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
 }
 
+// One output pixel from its ss x ss samples at src (rows sample_pitch apart).
 // VEC: the sample rows are aligned for the row's vector load and the output
 // for a dword store (checked by the launcher for the whole image).
 template <int SS, bool VEC>
-__global__ __launch_bounds__(kThreads) void sr_resolve_kernel(const uint8_t* __restrict__ samples, size_t sample_pitch,
-                                                              size_t sample_frame_stride, int width, int x_chunks,
-                                                              const int* __restrict__ blocks, int block_rows, int height,
-                                                              uint8_t* __restrict__ out, size_t pitch,
-                                                              size_t out_frame_stride) {
-    const int row = blockIdx.x / x_chunks;  // output row of the tile
-    const int x = (blockIdx.x % x_chunks) * kThreads + threadIdx.x;
-    if (blocks) {
-        const int b = blocks[row / block_rows];
-        if (b < 0 || b * block_rows + row % block_rows >= height) return;
-    }
-    if (x >= width) return;
-    const uint8_t* src = samples + (size_t)blockIdx.y * sample_frame_stride + (size_t)row * SS * sample_pitch +
-                         (size_t)x * (4 * SS);
-    uint8_t* dst = out + (size_t)blockIdx.y * out_frame_stride + (size_t)row * pitch + (size_t)x * 4;
+__device__ __forceinline__ void resolve_pixel(const uint8_t* __restrict__ src, size_t sample_pitch,
+                                              uint8_t* __restrict__ dst) {
     uint32_t even = 0, odd = 0;  // channels 0, 2 and 1, 3 in 16-bit fields
     if constexpr (VEC) {
 #pragma unroll
@@ -94,6 +82,60 @@ __global__ __launch_bounds__(kThreads) void sr_resolve_kernel(const uint8_t* __r
         dst[2] = (uint8_t)(v >> 16);
         dst[3] = (uint8_t)(v >> 24);
     }
+}
+
+template <int SS, bool VEC>
+__global__ __launch_bounds__(kThreads) void sr_resolve_kernel(const uint8_t* __restrict__ samples, size_t sample_pitch,
+                                                              size_t sample_frame_stride, int width, int x_chunks,
+                                                              const int* __restrict__ blocks, int block_rows, int height,
+                                                              uint8_t* __restrict__ out, size_t pitch,
+                                                              size_t out_frame_stride) {
+    const int row = blockIdx.x / x_chunks;  // output row of the tile
+    const int x = (blockIdx.x % x_chunks) * kThreads + threadIdx.x;
+    if (blocks) {
+        const int b = blocks[row / block_rows];
+        if (b < 0 || b * block_rows + row % block_rows >= height) return;
+    }
+    if (x >= width) return;
+    const uint8_t* src = samples + (size_t)blockIdx.y * sample_frame_stride + (size_t)row * SS * sample_pitch +
+                         (size_t)x * (4 * SS);
+    uint8_t* dst = out + (size_t)blockIdx.y * out_frame_stride + (size_t)row * pitch + (size_t)x * 4;
+    resolve_pixel<SS, VEC>(src, sample_pitch, dst);
+}
+
+// The masked resolve of sr_render_adaptive (adaptive.hip): one workgroup per
+// 16x16 output tile, lane t its pixel (t % 16, t / 16). Only the tiles with
+// mask[tile] != 0 are resolved, clipped to the frame: the sparse sample launch
+// wrote exactly their samples, so no other scratch is read, and the other
+// tiles of `out` keep the plain frame.
+template <int SS, bool VEC>
+__global__ __launch_bounds__(kThreads) void sr_resolve_masked_kernel(const uint8_t* __restrict__ samples,
+                                                                     size_t sample_pitch, int width, int height, int gx,
+                                                                     const uint8_t* __restrict__ mask,
+                                                                     uint8_t* __restrict__ out, size_t pitch) {
+    const int tile = blockIdx.x;
+    if (!mask[tile]) return;
+    const int x = (tile % gx) * 16 + (int)(threadIdx.x & 15), y = (tile / gx) * 16 + (int)(threadIdx.x >> 4);
+    if (x >= width || y >= height) return;
+    resolve_pixel<SS, VEC>(samples + (size_t)y * SS * sample_pitch + (size_t)x * (4 * SS), sample_pitch,
+                           out + (size_t)y * pitch + (size_t)x * 4);
+}
+
+template <int SS>
+hipError_t launch_resolve_masked(const uint8_t* samples, size_t sample_pitch, int width, int height,
+                                 const uint8_t* dev_mask, uint8_t* out, size_t pitch, hipStream_t stream) {
+    const int gx = (width + 15) / 16, gy = (height + 15) / 16;
+    if ((long long)gx * gy > 0x7fffffffLL) return hipErrorInvalidValue;
+    const size_t load = SS == 3 ? 4 : 4 * SS;
+    const bool vec = (((uintptr_t)samples | sample_pitch) & (load - 1)) == 0 && (((uintptr_t)out | pitch) & 3) == 0;
+    const dim3 grid((unsigned)(gx * gy));
+    if (vec)
+        hipLaunchKernelGGL((sr_resolve_masked_kernel<SS, true>), grid, dim3(kThreads), 0, stream, samples, sample_pitch,
+                           width, height, gx, dev_mask, out, pitch);
+    else
+        hipLaunchKernelGGL((sr_resolve_masked_kernel<SS, false>), grid, dim3(kThreads), 0, stream, samples,
+                           sample_pitch, width, height, gx, dev_mask, out, pitch);
+    return hipGetLastError();
 }
 
 template <int SS>
@@ -143,6 +185,20 @@ extern "C" hipError_t sr_resolve_box_device(const uint8_t* samples, size_t sampl
                                  out, pitch, out_frame_stride, n_frames, stream);
     default:
         return hipErrorInvalidValue;
+    }
+}
+
+// The flagged 16x16 tiles (dev_mask[ceil(height / 16)][ceil(width / 16)], bytes
+// 0 / 1) of a whole width x height frame from its full-size sample frame.
+extern "C" hipError_t sr_resolve_box_masked_device(const uint8_t* samples, size_t sample_pitch, int width, int height,
+                                                   int ss, const uint8_t* dev_mask, uint8_t* out, size_t pitch,
+                                                   hipStream_t stream) {
+    if (width <= 0 || height <= 0) return hipSuccess;
+    switch (ss) {
+    case 2: return launch_resolve_masked<2>(samples, sample_pitch, width, height, dev_mask, out, pitch, stream);
+    case 3: return launch_resolve_masked<3>(samples, sample_pitch, width, height, dev_mask, out, pitch, stream);
+    case 4: return launch_resolve_masked<4>(samples, sample_pitch, width, height, dev_mask, out, pitch, stream);
+    default: return hipErrorInvalidValue;
     }
 }
 

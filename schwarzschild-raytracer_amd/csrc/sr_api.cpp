@@ -124,6 +124,13 @@ struct sr_ctx {
     // sr_render_block_list_ss; resolve.hip reads it): grown on demand, reused
     uint8_t* d_ss = nullptr;
     size_t ss_bytes = 0;
+    // adaptive supersampling (sr_render_adaptive; adaptive.hip): the flagged
+    // output tiles (bytes) and the sparse launch's code list (one int per
+    // sample tile); grown on demand, reused
+    uint8_t* d_amask = nullptr;
+    size_t amask_n = 0;
+    int* d_acodes = nullptr;
+    size_t acodes_n = 0;
     // optional per-kernel timing: 4 events per frame (before integrate, after
     // integrate, after shade, after resume), a ring of `timing_cap` frames
     std::vector<hipEvent_t> tev;
@@ -677,6 +684,31 @@ int ensure_sample_scratch(sr_ctx* ctx, size_t bytes, hipStream_t s) {
     return SR_OK;
 }
 
+// Grows the tile mask and the code list of the adaptive launches the same way.
+int ensure_adaptive(sr_ctx* ctx, size_t tiles, size_t codes, hipStream_t s) {
+    if (tiles > ctx->amask_n) {
+        release(ctx, ctx->d_amask, s);
+        ctx->d_amask = nullptr;
+        ctx->amask_n = 0;
+        if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&ctx->d_amask), tiles, s))) {
+            ctx->d_amask = nullptr;
+            return SR_E_NOMEM;
+        }
+        ctx->amask_n = tiles;
+    }
+    if (codes > ctx->acodes_n) {
+        release(ctx, ctx->d_acodes, s);
+        ctx->d_acodes = nullptr;
+        ctx->acodes_n = 0;
+        if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&ctx->d_acodes), codes * sizeof(int), s))) {
+            ctx->d_acodes = nullptr;
+            return SR_E_NOMEM;
+        }
+        ctx->acodes_n = codes;
+    }
+    return SR_OK;
+}
+
 // Opacity bitmap of the texture array for the step loop's hit classification
 // (geodesic.hip hit_opacity): bit (layer, y, x) is set when every texel within
 // +-SR_OPQ_RADIUS of (x, y), wrapping like the sampler, has alpha 255. A
@@ -978,11 +1010,15 @@ int enter_stream(sr_ctx* ctx, hipStream_t s) {
 }
 
 // Renders the same rows of n_frames frames (cams[f]; output f at out + f *
-// frame_stride) in one launch of each kernel.
+// frame_stride) in one launch of each kernel. d_codes: a sparse launch of one
+// frame (sr_render_adaptive): the integrate and shade kernels run the tiles
+// of this device list of launch codes (one entry per tile of the grid, -1 =
+// none); no order of the grid's shape is looked up, learned or updated, and
+// split tiles do not apply to it.
 int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* params, int width, int height,
            int nrows, int row_base, int block_rows, int block_stride, uint8_t* out, size_t pitch,
            size_t frame_stride, float* dbg_rgba, int32_t* dbg_steps, sr_stream stream,
-           const int* d_block_list = nullptr, int32_t* d_wave_cost = nullptr) {
+           const int* d_block_list = nullptr, int32_t* d_wave_cost = nullptr, int* d_codes = nullptr) {
     if (!ctx) return SR_E_INVALID;
     if (!ctx->scene_set) return SR_E_NOT_READY;
     if (!cams || n_frames < 1) return SR_E_INVALID;
@@ -1017,6 +1053,8 @@ int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* pa
         if (!((double)q[0] * q[0] + (double)q[1] * q[1] + (double)q[2] * q[2] <= 1.0e4)) fr.win_ok = 0;
     }
     if (nrows < 0 || block_rows <= 0) return SR_E_INVALID;
+    if (d_codes && (n_frames != 1 || d_wave_cost)) return SR_E_INVALID;
+    if (d_codes) fr.split_tiles = 0;
     if (out && pitch < (size_t)width * 4) return SR_E_INVALID;
     if (n_frames > 1 && (!out || frame_stride < pitch * (size_t)nrows || dbg_rgba || dbg_steps)) return SR_E_INVALID;
     fr.out_frame_stride = (int64_t)frame_stride;
@@ -1037,7 +1075,9 @@ int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* pa
     if (rc != SR_OK) return rc;
     int* order = nullptr;
     int* cost = nullptr;
-    if (nrows > 0) {
+    if (d_codes) {
+        order = d_codes;  // no cost feedback: order_tiles does not run, last_order stays the plain frame's
+    } else if (nrows > 0) {
         rc = ensure_order(ctx, (width + 15) / 16, (nrows + 15) / 16, d_block_list, s, &order, &cost);
         if (rc != SR_OK) return rc;
         ctx->last_order = order;
@@ -1072,6 +1112,17 @@ extern "C" hipError_t sr_resolve_box_device(const uint8_t* samples, size_t sampl
 extern "C" void sr_resolve_box_host(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride, int width,
                                     int rows, int ss, uint8_t* out, size_t pitch, size_t out_frame_stride,
                                     int n_frames);
+
+// adaptive.hip
+extern "C" hipError_t sr_edge_tiles_device(const uint8_t* img, size_t pitch, int width, int height, int threshold,
+                                           int grow, uint8_t* dev_mask, hipStream_t stream);
+extern "C" hipError_t sr_adaptive_codes_device(const uint8_t* dev_mask, int width, int height, int ss, const int* order,
+                                               int n_order, int* codes, uint8_t* user_mask, hipStream_t stream);
+extern "C" void sr_edge_tiles_host(const uint8_t* img, size_t pitch, int width, int height, int threshold, int grow,
+                                   uint8_t* mask);
+extern "C" hipError_t sr_resolve_box_masked_device(const uint8_t* samples, size_t sample_pitch, int width, int height,
+                                                   int ss, const uint8_t* dev_mask, uint8_t* out, size_t pitch,
+                                                   hipStream_t stream);
 
 extern "C" {
 
@@ -1174,6 +1225,8 @@ void sr_destroy(sr_ctx* c) {
         for (auto& kv : c->tables) release(c, kv.second.dev, s);
         free_pixel_state(c, s);
         release(c, c->d_ss, s);
+        release(c, c->d_amask, s);
+        release(c, c->d_acodes, s);
         for (auto& kv : c->orders) {
             release(c, kv.second.order, s);
             release(c, kv.second.cost, s);
@@ -1646,6 +1699,73 @@ int sr_render_block_list_ss(sr_ctx* c, const sr_camera* cams, int n_frames, cons
     rc = ensure_block_list(c, blocks, n_blocks, reinterpret_cast<hipStream_t>(stream), &d);
     if (rc != SR_OK) return rc;
     return launch_ss(c, cams, n_frames, p, width, height, rows, 0, block_rows, d, ss, out, pitch, frame_stride, stream);
+}
+
+// ---- adaptive supersampling: the plain frame P into the caller's buffer,
+// the selection of its edge tiles (adaptive.hip), a sparse launch of the
+// sample frame for the flagged tiles only, and their masked resolve over P,
+// all on the caller's stream with no host wait
+
+int sr_edge_tiles(const uint8_t* rgba8, size_t pitch, int width, int height, int threshold, int grow,
+                  uint8_t* tile_mask, int on_device, sr_stream stream) {
+    if (!rgba8 || !tile_mask || width <= 0 || height <= 0 || grow < 0 || grow > 2) return SR_E_INVALID;
+    if (pitch < (size_t)width * 4) return SR_E_INVALID;
+    if ((long long)((width + 15) / 16) * ((height + 15) / 16) > INT32_MAX) return SR_E_INVALID;
+    if (!on_device) {
+        sr_edge_tiles_host(rgba8, pitch, width, height, threshold, grow, tile_mask);
+        return SR_OK;
+    }
+    const hipError_t e = sr_edge_tiles_device(rgba8, pitch, width, height, threshold, grow, tile_mask,
+                                              reinterpret_cast<hipStream_t>(stream));
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
+}
+
+int sr_render_adaptive(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int ss,
+                       int threshold, int grow, uint8_t* out, size_t pitch, uint8_t* dev_tile_mask,
+                       sr_stream stream) {
+    if (ss < 2 || ss > SR_MAX_SUPERSAMPLE || grow < 0 || grow > 2 || !out) return SR_E_INVALID;
+    int rc = check_frames(c, cam, 1, p, width, height);
+    if (rc != SR_OK) return rc;
+    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > (1 << 24) / ss) return SR_E_INVALID;
+    const size_t tiles = (size_t)((width + 15) / 16) * (size_t)((height + 15) / 16);
+    const size_t stiles = (size_t)((ss * width + 15) / 16) * (size_t)((ss * height + 15) / 16);
+    if (stiles > ((size_t)1 << 22)) return SR_E_INVALID;  // a launch code is tile << 8 in an int
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (threshold >= 255) {  // no tile can be flagged: the plain frame, no sample work
+        rc = launch(c, cam, 1, p, width, height, height, 0, height, 0, out, pitch, 0, nullptr, nullptr, stream);
+        if (rc != SR_OK || !dev_tile_mask) return rc;
+        hipError_t e = hipMemsetAsync(dev_tile_mask, 0, tiles, s);
+        if (hip_ok(e)) e = hipEventRecord(c->order_ev, s);
+        return hip_ok(e) ? SR_OK : SR_E_HIP;
+    }
+    rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    // every buffer of the call ahead of its first launch: SR_E_NOMEM with
+    // nothing launched. The pixel state is the whole sample frame's (the
+    // integrate kernel's ids are the frame's), which holds the plain frame's.
+    const size_t spitch = (size_t)width * 4 * (size_t)ss;
+    rc = ensure_sample_scratch(c, spitch * (size_t)height * (size_t)ss, s);
+    if (rc == SR_OK) rc = ensure_adaptive(c, tiles, stiles, s);
+    if (rc == SR_OK) rc = ensure_pixel_state(c, stiles * 256, s);
+    if (rc != SR_OK) return rc;
+    // P: the ordinary launch, which runs and learns the plain frame's order
+    rc = launch(c, cam, 1, p, width, height, height, 0, height, 0, out, pitch, 0, nullptr, nullptr, stream);
+    if (rc != SR_OK) return rc;
+    hipError_t e = sr_edge_tiles_device(out, pitch, width, height, threshold, grow, c->d_amask, s);
+    // the sample tiles in the order P's launch just learned (its shade kernel wrote it): costliest first
+    if (hip_ok(e) && (!c->last_order || c->last_slots > (size_t)INT32_MAX)) e = hipErrorInvalidValue;
+    if (hip_ok(e))
+        e = sr_adaptive_codes_device(c->d_amask, width, height, ss, c->last_order, (int)c->last_slots, c->d_acodes,
+                                     dev_tile_mask, s);
+    if (!hip_ok(e)) return SR_E_HIP;
+    // S, the flagged tiles' part of it
+    rc = launch(c, cam, 1, p, ss * width, ss * height, ss * height, 0, ss * height, 0, c->d_ss, spitch, 0, nullptr,
+                nullptr, stream, nullptr, nullptr, c->d_acodes);
+    if (rc != SR_OK) return rc;
+    e = sr_resolve_box_masked_device(c->d_ss, spitch, width, height, ss, c->d_amask, out, pitch, s);
+    // again at the end of the whole: a launch on another stream waits for the resolve too
+    if (hip_ok(e)) e = hipEventRecord(c->order_ev, s);
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
 }
 
 int sr_render_debug(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int row_begin,

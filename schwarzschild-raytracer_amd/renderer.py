@@ -221,6 +221,36 @@ class Renderer:
         )
         return out
 
+    def render_adaptive(self, cam: abi.Camera, params: abi.Params, width: int, height: int, ss: int, threshold: int,
+                        grow: int = 0, out=None, stream=None):
+        """The whole frame with ss x ss samples only in the 16x16 tiles that
+        hold an edge of the plain frame (sr_render_adaptive) ->
+        ([height, width, 4] frame, uint8 [ceil(H / 16), ceil(W / 16)] flagged tiles)."""
+        if out is None:
+            out = self.torch.empty((height, width, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and out.numel() >= height * width * 4
+        mask = self.torch.empty(((height + 15) // 16, (width + 15) // 16), dtype=self.torch.uint8, device=self.tdev)
+        abi.check(
+            self.lib.sr_render_adaptive(self.ctx, C.byref(cam), C.byref(params), width, height, int(ss), int(threshold),
+                                        int(grow), C.c_void_p(out.data_ptr()), width * 4, C.c_void_p(mask.data_ptr()),
+                                        self._stream(stream)),
+            "sr_render_adaptive",
+        )
+        return out, mask
+
+    def edge_tiles(self, frame, threshold: int, grow: int = 0, stream=None):
+        """sr_edge_tiles on the device: an [H, W, 4] uint8 tensor on this device
+        -> its flagged tiles, uint8 [ceil(H / 16), ceil(W / 16)]. Asynchronous."""
+        assert frame.dtype == self.torch.uint8 and frame.dim() == 3 and frame.shape[2] == 4 and frame.is_contiguous()
+        h, w = int(frame.shape[0]), int(frame.shape[1])
+        mask = self.torch.empty(((h + 15) // 16, (w + 15) // 16), dtype=self.torch.uint8, device=self.tdev)
+        abi.check(
+            self.lib.sr_edge_tiles(C.c_void_p(frame.data_ptr()), w * 4, w, h, int(threshold), int(grow),
+                                   C.c_void_p(mask.data_ptr()), 1, self._stream(stream)),
+            "sr_edge_tiles",
+        )
+        return mask
+
     def render_debug(self, cam: abi.Camera, params: abi.Params, width: int, height: int, row_begin: int = 0,
                      row_end: int | None = None, stream=None):
         """(float RGBA FragColor, RGBA8, executed steps) for rows [row_begin, row_end)."""

@@ -7,6 +7,8 @@ hyperbolic trajectory (src/main.cpp:404-410) in batched launches.
   python tools/render.py --out frame.png [--width 1920 --height 1080 --max-steps 2000]
   python tools/render.py --flyby 8 --out flyby_%02d.png
   python tools/render.py --ssaa 2 --out frame_ss2.png      (2 x 2 samples per pixel, box resolve)
+  python tools/render.py --ssaa 4 --adaptive 32 --grow 1 --out frame_a4.png
+                                  (4 x 4 samples only in the 16x16 tiles with an edge above 32 levels)
 """
 import argparse
 import sys
@@ -31,7 +33,14 @@ def main():
     ap.add_argument("--flyby", type=int, default=0, help="frames along the hyperbolic flyby (0: the default camera)")
     ap.add_argument("--ssaa", type=int, default=1, choices=[1, 2, 3, 4],
                     help="supersampling: N x N samples per pixel, box resolve (sr_render_ss; 1: off)")
+    ap.add_argument("--adaptive", type=int, default=None, metavar="THRESHOLD",
+                    help="with --ssaa 2 .. 4: supersample only the 16x16 tiles of the plain frame that hold two "
+                         "neighbouring pixels more than THRESHOLD levels apart in a channel (sr_render_adaptive)")
+    ap.add_argument("--grow", type=int, default=0, choices=[0, 1, 2],
+                    help="--adaptive: dilate the flagged tiles this many times by their 3x3 neighbourhood")
     args = ap.parse_args()
+    if args.adaptive is not None and (args.ssaa < 2 or args.flyby > 0):
+        ap.error("--adaptive needs --ssaa 2 .. 4 and a single frame (no --flyby)")
     import torch
 
     import srpkg
@@ -52,7 +61,12 @@ def main():
     params.crosshair = 1 if args.crosshair else 0
     W, H = args.width, args.height
     if args.flyby <= 0:
-        frame = r.render_ss(abi.default_camera(), params, W, H, args.ssaa)
+        if args.adaptive is not None:
+            frame, tiles = r.render_adaptive(abi.default_camera(), params, W, H, args.ssaa, args.adaptive, args.grow)
+            torch.cuda.synchronize()
+            print(f"supersampled {int(tiles.sum())} of {tiles.numel()} tiles")
+        else:
+            frame = r.render_ss(abi.default_camera(), params, W, H, args.ssaa)
         torch.cuda.synchronize()
         abi.write_png(args.out, frame.cpu().numpy())
         print(f"wrote {args.out}")
