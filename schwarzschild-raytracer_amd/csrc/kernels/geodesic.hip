@@ -665,6 +665,9 @@ __device__ __forceinline__ float nmin(float m, float e) { return __builtin_eleme
 #ifndef SR_COAST  // the RK4-only fast loop of waves whose every budget is +inf (integrate)
 #define SR_COAST 1
 #endif
+#ifndef SR_RETIRE_COAST  // lanes whose ray ends at a u_f crossing retire inside the coasting loop (integrate)
+#define SR_RETIRE_COAST 1
+#endif
 // The budget state's LDS rows (one column per thread) for an
 // instantiation with NB budget slots and NC budgeted cylinders: E[0..NB],
 // then pa[k], pb[k] (rows PA0 + 2k, + 1) and the slab budgets H[k] (SLAB0 +
@@ -2585,45 +2588,60 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         im = i - 1;
     };
     bool force = false;  // this lane's next chord is charged exactly (new orbital frame)
+    // frag:891-912, the reseed of a lane whose u dropped below u_f, at the top
+    // of step i (up = u after step i - 2). Returns the status that ends the
+    // ray (ST_BG / ST_FLAT: r.steps, r.rd and r.ro are final) or -1: the ray
+    // goes on in its new orbital frame, its next chord forced. The one copy,
+    // called at the top of the step loop and where the coasting loop retires
+    // lanes in place (SR_RETIRE_COAST).
+    auto reseed = [&](int i) -> int {
+        r.i = i;
+        r.steps = sbase + i + 1;
+        settle_prev(i);
+        // the new orbital plane has its own coordinates: charge the
+        // displacement from the old centre to the chord start r.ro
+        // here, the new chord at the forced event (reseeded)
+        if (CULL)
+        {
+            const float ocx = bs.cx(), ocy = bs.cy();
+            bs.setT(__builtin_fmaf(len(r.ro - (r.nv * ocx + r.tv * ocy)), 1.0101f,
+                                   3.0e-6f * (fabsf(ocx) + fabsf(ocy) + 1.0f)));
+        }
+        float lam;
+        if (!sphere_lambda_r2(r.ro, r.rd, F3(0.0f, 0.0f, 0.0f), fr.uf_radius2, -1.0f, lam))
+            return flat_misses(sc, r.ro, r.rd) ? ST_BG : ST_FLAT;
+        const f3 q = r.ro + r.rd * lam;  // sphere_intersect's point (computed past the exit)
+        r.nv = nrm(q);
+        if (fabsf(dot(r.rd, r.nv)) >= 1.0f - SR_EPS) return flat_misses(sc, r.ro, r.rd) ? ST_BG : ST_FLAT;
+        r.tv = nrm(cross(cross(r.nv, r.rd), r.nv));
+        r.u = 1.0f / len(q);
+        r.du = -r.u * dot(r.rd, r.nv) / dot(r.rd, r.tv);
+        if (CULL) budget_frame(sc, bs, r.nv, r.tv, fr.xplane_s, fr.xlow_need, fr.xperi_e,
+                                  orbit_e(r.u, r.du));
+        force = true;  // the chord starts at the exact r.ro
+        return -1;
+    };
+    // the coasting loop left with its continuing lanes already reseeded for
+    // step i: u_f is not compared again before the next top (wave-uniform)
+    bool reseeded_in_loop = false;
     int i = r.i;
     SR_PROBE(LoopProbe lp(i); SR_PROF_LOOP_START(r, bs, prof_bi_));
     for (;;) {
         if (RECORD) i = __builtin_amdgcn_readfirstlane(i);  // every lane started at step 0: keep i scalar
         // (sr_resume_kernel's lanes are unrelated rays at their own steps)
         if (i >= N) break;
-        // frag:891-912, the top of step i (the fast loop below leaves a step
-        // early whenever some lane's u drops below u_f, so this is where
-        // every reseed happens)
+        // the top of step i (the fast loop below leaves a step early whenever
+        // some lane's u drops below u_f, so this and the coasting loop's
+        // retirement are where every reseed happens)
         SR_PT(21);
-        if (__ballot(r.u < fr.u_f)) {
+        if (!reseeded_in_loop && __ballot(r.u < fr.u_f)) {
             if (r.u < fr.u_f) {
-                r.i = i;
-                r.steps = sbase + i + 1;
-                settle_prev(i);
-                // the new orbital plane has its own coordinates: charge the
-                // displacement from the old centre to the chord start r.ro
-                // here, the new chord at the forced event (reseeded)
-                if (CULL)
-                {
-                    const float ocx = bs.cx(), ocy = bs.cy();
-                    bs.setT(__builtin_fmaf(len(r.ro - (r.nv * ocx + r.tv * ocy)), 1.0101f,
-                                           3.0e-6f * (fabsf(ocx) + fabsf(ocy) + 1.0f)));
-                }
-                float lam;
-                if (!sphere_lambda_r2(r.ro, r.rd, F3(0.0f, 0.0f, 0.0f), fr.uf_radius2, -1.0f, lam))
-                    return flat_misses(sc, r.ro, r.rd) ? ST_BG : ST_FLAT;
-                const f3 q = r.ro + r.rd * lam;  // sphere_intersect's point (computed past the exit)
-                r.nv = nrm(q);
-                if (fabsf(dot(r.rd, r.nv)) >= 1.0f - SR_EPS) return flat_misses(sc, r.ro, r.rd) ? ST_BG : ST_FLAT;
-                r.tv = nrm(cross(cross(r.nv, r.rd), r.nv));
-                r.u = 1.0f / len(q);
-                r.du = -r.u * dot(r.rd, r.nv) / dot(r.rd, r.tv);
-                if (CULL) budget_frame(sc, bs, r.nv, r.tv, fr.xplane_s, fr.xlow_need, fr.xperi_e,
-                                          orbit_e(r.u, r.du));
-                force = true;  // the chord starts at the exact r.ro
+                const int st = reseed(i);
+                if (st >= 0) return st;
             }
             SR_PT(1);
         }
+        reseeded_in_loop = false;
         // ---- fast loop: RK4, the ball test of the step's end point and
         // the u compares per step, the same instructions on every lane and
         // wave-uniform exits only. The wave leaves with step i computed but
@@ -2754,39 +2772,105 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         // (T is reset at that re-anchor; rB is restored on the way out), so
         // the iterates are the same. Only outward lanes (u < 0.6 falling)
         // coast: u stays finite.
-        auto coast = [&]() {
-            e = ldc(tp);
-            for (;;) {
-                float4 nx[FU];
+        //
+        // Retirement (SR_RETIRE_COAST, sr_integrate_kernel): most exits of
+        // this loop are a few lanes crossing u_f a step after their
+        // wave-mates, whose reseed ends their ray (1.63 M of the headline
+        // frame's pixels end this way, at 89 k exit steps). Leaving for them
+        // took the whole wave through the slow path (no event, no chord) and
+        // the loop's set-up again. When the exit step is nothing but that - no
+        // lane of the wave has an event (the slow path's own predicate), u < 0
+        // (recover_up's replay), a certain shell crossing or the loop's end
+        // ahead - the step is applied on the way out as the slow path applies
+        // it, the lanes below u_f run the loop top's reseed (the one copy)
+        // with the operands it would have got, and the wave enters the loop
+        // again: one copy of the handler, off the loop's own code. A lane
+        // whose ray ends there is parked: its status and step count go into
+        // `park` (-1: live), r.rd / r.ro are final, and it runs on at the RK4
+        // fixed point (u, u') = (0, 0) with the bounds (-inf, +inf), which
+        // fires no exit and makes no NaN (every product is with +-0). Parked
+        // lanes return when the wave next leaves the loop. A lane whose
+        // reseed goes on (its line re-enters the u_f sphere) takes the wave
+        // out, to where the step loop stands after its own reseed block.
+        // Returns the parked lane's packed status (status | steps << 3) or -1.
+        auto coast = [&]() -> int {
+            constexpr bool RETIRE = SR_RETIRE_COAST && RECORD;
+            int park = -1;
+            float lo = ulo, hi = uhi;
+            for (;;) {  // (entered again after a retirement)
+                e = ldc(tp);
+                for (;;) {
+                    float4 nx[FU];
 #pragma unroll
-                for (int k = 0; k < FU; k++) nx[k] = ldc(tp + 1 + k);
-                __builtin_amdgcn_sched_barrier(0);
-                bool leave = false;
+                    for (int k = 0; k < FU; k++) nx[k] = ldc(tp + 1 + k);
+                    __builtin_amdgcn_sched_barrier(0);
+                    bool leave = false;
 #pragma unroll
-                for (int k = 0; k < FU && !leave; k++) {
-                    rk4_step(r.u, r.du, e.x, e.y, un, dun);  // frag:914-919
-                    SR_STAT(0, 1);
-                    SR_STAT(11, 1);  // coasting wave-steps
-                    SR_STAT(13, __popcll(__ballot(1)));
-                    if (__ballot(!(un >= ulo && un <= uhi))) {  // NaN leaves too
+                    for (int k = 0; k < FU && !leave; k++) {
+                        rk4_step(r.u, r.du, e.x, e.y, un, dun);  // frag:914-919
+                        SR_STAT(0, 1);
+                        SR_STAT(11, 1);  // coasting wave-steps
+                        SR_STAT(13, __popcll(__ballot(1)));
+                        if (__ballot(!(un >= lo && un <= hi))) {  // NaN leaves too
 #pragma unroll
-                        for (int j = k; j < FU; j++) asm volatile("; keep %0" ::"s"(nx[j].x));
-                        leave = true;
-                    } else {
+                            for (int j = k; j < FU; j++) asm volatile("; keep %0" ::"s"(nx[j].x));
+                            leave = true;
+                        } else {
+                            r.u = un;
+                            r.du = dun;
+                            tp += 1;
+                            e = nx[k];
+                            leave = ++i >= N;
+                        }
+                    }
+                    if (leave) break;
+                }
+                if constexpr (RETIRE) {
+                    // step i is computed and not applied (or the loop ended: i = N).
+                    // The slow path's event of this step (vb < 0 here), its u < 0
+                    // exit and its certain shell crossing, on live lanes
+                    const bool stays = park < 0 && (un > hi || (un < SR_BH_ULO2 && BS::inner(hi)) ||
+                                                    (SR_XPLANE && un < 0.5f * fr.u_f) ||
+                                                    !(un < 1.0e30f && r.u < 1.0e30f) || un < 0.0f ||
+                                                    (BS::inner(hi) && un >= SR_BH_UIN3));
+                    if (i + 1 < N && !__ballot(stays)) {
+                        SR_PROBE(SR_RETIRE_STAT(1, 1));  // exit steps retired here
+                        up = r.u;
                         r.u = un;
                         r.du = dun;
                         tp += 1;
-                        e = nx[k];
-                        leave = ++i >= N;
+                        ++i;
+                        bool goes_on = false;
+                        if (park < 0 && r.u < fr.u_f) {  // the loop top's test, at the top of step i
+                            const int st = reseed(i);
+                            if (st >= 0) {
+                                park = st | (r.steps << 3);
+                                r.u = 0.0f;
+                                r.du = 0.0f;
+                                lo = -INFINITY;
+                                hi = INFINITY;
+                            } else {
+                                goes_on = true;
+                            }
+                        }
+                        SR_PROBE(SR_RETIRE_STAT(2, __popcll(__ballot(park >= 0 && (park >> 3) == sbase + i + 1))));
+                        if (__ballot(goes_on)) {
+                            SR_PROBE(SR_RETIRE_STAT(3, 1));  // left because a reseed went on
+                            reseeded_in_loop = true;
+                        } else if (__ballot(park < 0)) {
+                            continue;  // on with step i
+                        }
+                        // (no live lane left: every lane returns its status)
                     }
                 }
-                if (leave) break;
+                break;
             }
             // the state the full loop leaves: step i's radius, no charge (every budget is +inf)
             rA = __builtin_amdgcn_rcpf(r.u);
             rB = __builtin_amdgcn_rcpf(un);
             par = 0;
             vb = -1.0f;  // inside every (infinite) budget
+            return park;
         };
         // The fast loop does not carry `up` (u after step i - 2): the copy
         // cost a register move per step in its rotation (42.3 -> 41.7 VALU
@@ -2814,16 +2898,24 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         using I0 = std::integral_constant<int, 0>;
         using I1 = std::integral_constant<int, 1>;
         using I2 = std::integral_constant<int, 2>;
+        int park = -1;  // a lane the coasting loop retired: status | steps << 3
         if constexpr (NC > 0) {
             if (cm_iter) fast(I2{});
             else if (any_cm) fast(I1{});
-            else if (CULL && SR_COAST && !__ballot(!(lim0 == INFINITY))) coast();
+            else if (CULL && SR_COAST && !__ballot(!(lim0 == INFINITY))) park = coast();
             else fast(I0{});
         } else {
-            if (CULL && SR_COAST && !__ballot(!(lim0 == INFINITY))) coast();
+            if (CULL && SR_COAST && !__ballot(!(lim0 == INFINITY))) park = coast();
             else fast(I0{});
         }
         SR_PT(0);
+        if (SR_RETIRE_COAST && RECORD) {
+            if (park >= 0) {  // the divergent return of the lanes retired in the loop
+                r.steps = park >> 3;
+                return park & 7;
+            }
+            if (reseeded_in_loop) continue;  // at the top of step i, its reseeds done
+        }
         if (i >= N) {
             SR_PROBE(SR_STAT_STEPHIST(56, N - 1 - ick); SR_STAT_STEPHIST(57, 1));  // recover_up's replayed steps
             up = recover_up(N);
@@ -2897,7 +2989,10 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         const bool reseeded = force;
         force = false;
         do {  // `break`: on to step i + 1
-            if (!__ballot(event)) break;
+            if (!__ballot(event)) {
+                SR_PROBE(SR_RETIRE_STAT(0, 1));
+                break;
+            }
             uint32_t reach = 0xffffffffu;
             uint32_t trmask = 0xffffffffu;  // test-ray parts this lane's chord may reach (budget_event)
             const f2 p1 = phi_cs(i - 1);

@@ -15,7 +15,7 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-NREC = 24  # SR_PROF_N
+NREC = 28  # SR_PROF_N
 SECTIONS = ["fast", "reseed", "slow_entry", "budget_phase1", "exact_chord", "hit_class", "budget_phase2"]
 
 
@@ -69,6 +69,11 @@ def main():
     out["tail_top_all_waves"] = int(t[ok, 21].sum())
     out["budget_init_all_waves"] = int(t[ok, 22].sum())  # builds since round 4 (0 before)
     out["ray_setup_all_waves"] = int(t[ok, 23].sum())  # kernel start to integrate: launch code, pixel, ray
+    # the fast-loop exits that are no budget event (probes.h SR_RETIRE_STAT)
+    out["non_event_slow_entries_all_waves"] = int(t[ok, 24].sum())
+    out["retired_exit_steps_all_waves"] = int(t[ok, 25].sum())
+    out["lanes_parked_all_waves"] = int(t[ok, 26].sum())
+    out["retired_left_for_continuing_reseed_all_waves"] = int(t[ok, 27].sum())
     out["unaccounted_cycles_all_waves"] = int(total[ok].sum() - sums.sum() - t[ok, 20].sum() - t[ok, 21].sum()
                                               - t[ok, 22].sum() - t[ok, 23].sum())
     gx = (1920 + 15) // 16
@@ -78,7 +83,8 @@ def main():
          "total_cycles": int(total[w]), "cycles_per_step": round(float(total[w]) / max(1, int(steps[w])), 1),
          **{k: int(v) for k, v in zip(SECTIONS, t[w, :7])}, "reanchors_by_slot": [int(v) for v in t[w, 8:16]],
          "events": int(t[w, 16]), "events_slot0_only": int(t[w, 17]), "lane_slot0_spends": int(t[w, 18]),
-         "slow_entries": int(t[w, 19]), "phase1_ballots": int(t[w, 20]), "tail_top": int(t[w, 21])}
+         "slow_entries": int(t[w, 19]), "phase1_ballots": int(t[w, 20]), "tail_top": int(t[w, 21]),
+         "non_event_slow_entries": int(t[w, 24]), "retired_exit_steps": int(t[w, 25]), "lanes_parked": int(t[w, 26])}
         for w in top]
     print(json.dumps(out, indent=1))
     r.close()

@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--stephist", action="store_true", help="an SR_STATS_STEPHIST build (counters 44..55)")
     ap.add_argument("--near", action="store_true", help="an SR_STATS_NEAR build (counters 44..61)")
     ap.add_argument("--xcyl", action="store_true", help="an SR_STATS_XCYL build (counters 44..54)")
+    ap.add_argument("--retire", action="store_true", help="an SR_STATS_RETIRE build (counters 44..47)")
     args = ap.parse_args()
     os.environ["SR_LIB"] = str(Path(args.lib).resolve())
     import torch  # noqa: F401  (HIP runtime up before the library)
@@ -113,6 +114,11 @@ def main():
             out["cyl_events"] = int(hi[17])
             out["cyl_alone_events"] = int(hi[22])
             out["cyl_alone_events_all_lanes_beyond_br_plus"] = dict(zip(ds, [int(hi[18 + k]) for k in range(4)]))
+        if args.retire:  # an SR_STATS_RETIRE build: fast-loop exits that are no budget event
+            for k in ("event_lanes", "events_bh_window_only", "interval1_small_budget_lanes_by_slot"):
+                out.pop(k, None)
+            out["retire"] = dict(zip(["non_event_slow_entries", "retired_exit_steps", "lanes_parked",
+                                      "retired_left_for_continuing_reseed"], [int(hi[12 + k]) for k in range(4)]))
         if args.trig:  # an SR_STATS_TRIG build: counters 44..63 hold the lanes that spent each slot
             for k in ("event_lanes", "events_bh_window_only", "interval1_small_budget_lanes_by_slot"):
                 out.pop(k, None)
