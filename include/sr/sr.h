@@ -420,6 +420,91 @@ int sr_resolve_box(const uint8_t* samples, size_t sample_pitch, size_t sample_fr
                    int width, int rows, int ss, uint8_t* out, size_t pitch, size_t out_frame_stride,
                    int n_frames, int on_device, sr_stream stream);
 
+/* ---- Sample phases and progressive supersampling (not in the reference). S
+ * is the sample frame exactly as sr_render_ss defines it: the frame this
+ * library renders for (ss * width) x (ss * height) with the same scene,
+ * camera, params, textures and test ray, ss in 1 .. SR_MAX_SUPERSAMPLE.
+ *
+ * Phase image: phase (i, j), i and j in 0 .. ss - 1, is the width x height
+ * image of one sub-sample position of every output pixel,
+ *
+ *   phase(i, j)[y][x] = S[ss*y + j][ss*x + i]     (all four bytes)
+ *
+ *  - the crosshair, the noise mask (percent_black) and the split modes
+ *    (raytrace_type) are those of S, evaluated at the sample's own position;
+ *  - ss == 1, phase (0, 0) is the plain frame, byte for byte.
+ * A phase launch has the grid, the pixel state (208 bytes per OUTPUT pixel)
+ * and the launch order of a plain width x rows frame: the order is the one
+ * cached for that shape, shared with plain frames of it, learned and used as
+ * sr_render does; sr_set_split, sr_set_latency_mode and culling apply as to
+ * any frame of that size.
+ *
+ * Accumulator: caller-owned memory, uint16_t[rows][width][4] (row r at
+ * accum + r * accum_pitch_bytes); base address and pitch must be multiples
+ * of 8. RGBA8 images are added channel by channel in plain 16-bit adds
+ * (modulo 2^16): SR_MAX_ACCUM_PASSES (256) images cannot wrap, 256 * 255 fits.
+ *
+ * Resolve: out[y][x][c] = min(255, (acc[y][x][c] + n / 2) div n) in integers,
+ * n in 1 .. SR_MAX_ACCUM_PASSES. With n = ss * ss over all phases of a grid
+ * this is the box rule above: the result equals sr_render_ss's frame byte for
+ * byte, in whatever order and grouping the phases were added. Any prefix of
+ * the phases resolved with its own count is a displayable frame, each pass at
+ * about the cost of one plain frame, and one phase at a time needs no more
+ * memory than a plain frame plus the accumulator, at any ss. */
+#define SR_MAX_ACCUM_PASSES 256
+
+/* sr_render with the phase mapping: rows [row_begin, row_end) of phase
+ * (phase_x, phase_y) of the ss x ss grid. No scratch beyond a plain frame's.
+ * SR_E_INVALID for ss outside 1 .. SR_MAX_SUPERSAMPLE or a phase coordinate
+ * outside 0 .. ss - 1; otherwise as sr_render. */
+int sr_render_phase(sr_ctx* ctx, const sr_camera* cam, const sr_params* params, int width, int height,
+                    int row_begin, int row_end, int ss, int phase_x, int phase_y, uint8_t* dev_rgba8,
+                    size_t pitch_bytes, sr_stream stream);
+
+/* Renders n_phases (1 .. 32) phases of one camera in ONE launch (the frames
+ * of a batch, as sr_render_blocks_batch carries cameras) and adds them to the
+ * accumulator's rows [0, row_end - row_begin) (reset != 0: stores their sum
+ * instead, the accumulator is not read), all asynchronous on `stream` with no
+ * host synchronisation. phases: n_phases pairs of bytes {x, y} (host memory,
+ * read during the call). Scratch: the context's sample buffer (see above),
+ * 4 * width * rows * n_phases bytes, and the pixel state of n_phases plain
+ * frames. SR_E_INVALID for ss outside 1 .. SR_MAX_SUPERSAMPLE, a phase
+ * coordinate outside 0 .. ss - 1, null pointers, n_phases < 1,
+ * accum_pitch_bytes < 8 * width or a misaligned accumulator; SR_E_CAPACITY
+ * above 32 phases; SR_E_NOT_READY and SR_E_NOMEM (nothing launched) as for
+ * sr_render_ss. */
+int sr_render_accumulate(sr_ctx* ctx, const sr_camera* cam, const sr_params* params, int width, int height,
+                         int row_begin, int row_end, int ss, const uint8_t* phases, int n_phases, int reset,
+                         uint16_t* dev_accum, size_t accum_pitch_bytes, sr_stream stream);
+
+/* The add alone: n_images (1 .. SR_MAX_ACCUM_PASSES) RGBA8 images of width x
+ * rows (row r of image k at images + k * image_stride + r * pitch; the
+ * pointer, pitch and stride multiples of 4) added to the accumulator, or
+ * stored when reset != 0. on_device != 0: device pointers, a kernel on
+ * `stream`, asynchronous; 0: host memory, synchronous (the same rule in plain
+ * C++). SR_E_INVALID for null pointers, sizes <= 0, a short pitch or stride,
+ * a misaligned pointer or n_images out of range. */
+int sr_accum_add(const uint8_t* images, size_t pitch, size_t image_stride, int n_images, int width, int rows,
+                 int reset, uint16_t* accum, size_t accum_pitch, int on_device, sr_stream stream);
+
+/* The resolve alone, by the rule above, into RGBA8 rows (out and pitch
+ * multiples of 4). on_device as for sr_accum_add. SR_E_INVALID for null
+ * pointers, sizes <= 0, a short pitch, a misaligned pointer or n outside
+ * 1 .. SR_MAX_ACCUM_PASSES. */
+int sr_accum_resolve(const uint16_t* accum, size_t accum_pitch, int width, int rows, int n, uint8_t* out,
+                     size_t pitch, int on_device, sr_stream stream);
+
+/* Progressive order (host only): pass k (0 .. ss*ss - 1) of an ss x ss grid
+ * renders phase (*phase_x, *phase_y); every prefix spreads over the pixel:
+ *   ss 1: (0,0)
+ *   ss 2: (0,0) (1,1) (1,0) (0,1)
+ *   ss 3: (1,1) (0,0) (2,2) (2,0) (0,2) (1,0) (1,2) (0,1) (2,1)
+ *   ss 4: (0,0) (2,2) (2,0) (0,2) (1,1) (3,3) (3,1) (1,3)
+ *         (1,0) (3,2) (3,0) (1,2) (0,1) (2,3) (2,1) (0,3)
+ * (ss 2 and 4: the 2x2 and 4x4 ordered-dither matrices read by rank).
+ * SR_E_INVALID for ss or k out of range or a null pointer. */
+int sr_phase_order(int ss, int k, int* phase_x, int* phase_y);
+
 /* ---- Adaptive supersampling (not in the reference): supersample only the
  * 16x16 output tiles of the frame that hold an edge. Inputs: one camera and
  * one whole width x height frame, ss in 2 .. SR_MAX_SUPERSAMPLE, threshold

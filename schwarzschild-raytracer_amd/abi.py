@@ -209,8 +209,16 @@ SIGNATURES = {
     "sr_resolve_box": (_i, [_p, C.c_size_t, C.c_size_t, _i, _i, _i, _p, C.c_size_t, C.c_size_t, _i, _i, _p]),
     "sr_render_adaptive": (_i, [_p, C.POINTER(Camera), C.POINTER(Params), _i, _i, _i, _i, _i, _p, C.c_size_t, _p, _p]),
     "sr_edge_tiles": (_i, [_p, C.c_size_t, _i, _i, _i, _i, _p, _i, _p]),
+    "sr_render_phase": (_i, [_p, C.POINTER(Camera), C.POINTER(Params), _i, _i, _i, _i, _i, _i, _i, _p, C.c_size_t, _p]),
+    "sr_render_accumulate": (_i, [_p, C.POINTER(Camera), C.POINTER(Params), _i, _i, _i, _i, _i, _p, _i, _i, _p,
+                                  C.c_size_t, _p]),
+    "sr_accum_add": (_i, [_p, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _p, C.c_size_t, _i, _p]),
+    "sr_accum_resolve": (_i, [_p, C.c_size_t, _i, _i, _i, _p, C.c_size_t, _i, _p]),
+    "sr_phase_order": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
 }
 MAX_SUPERSAMPLE = 4
+MAX_BATCH = 32  # frames (cameras or phases) of one launch
+MAX_ACCUM_PASSES = 256
 # exported beside the header set (parity tooling)
 EXTRA_SIGNATURES = {
     "sr_debug_set_culling": (_i, [_p, _i]),
@@ -308,6 +316,65 @@ def edge_tiles(frame, threshold: int, grow: int = 0):
     out = np.empty(((h + 15) // 16, (w + 15) // 16), dtype=np.uint8)
     check(load().sr_edge_tiles(a.ctypes.data, a.strides[0], w, h, int(threshold), int(grow), out.ctypes.data, 0, None),
           "sr_edge_tiles")
+    return out
+
+
+def phase_order(ss: int):
+    """sr_phase_order: the ss * ss phases (x, y) of an ss x ss grid in
+    progressive order."""
+    lib = load()
+    out = []
+    x, y = C.c_int(), C.c_int()
+    for k in range(ss * ss if 1 <= ss <= MAX_SUPERSAMPLE else 1):
+        check(lib.sr_phase_order(int(ss), k, C.byref(x), C.byref(y)), "sr_phase_order")
+        out.append((x.value, y.value))
+    return out
+
+
+def _aligned_rows(rows: int, pitch: int, align: int = 8):
+    """A zeroed host buffer of rows x pitch bytes whose base is a multiple of `align`."""
+    import numpy as np
+
+    raw = np.zeros(rows * pitch + align, dtype=np.uint8)
+    o = (-raw.ctypes.data) % align
+    return raw[o:o + rows * pitch]
+
+
+def accum_add(images, accum=None, reset: bool = False):
+    """sr_accum_add's host form: uint8 images [n, rows, W, 4] (or one [rows, W,
+    4]) added to the uint16 accumulator [rows, W, 4] (host arrays; a new zero
+    accumulator when None) -> the accumulator."""
+    import numpy as np
+
+    a = np.ascontiguousarray(images, dtype=np.uint8)
+    if a.ndim == 3:
+        a = a[None]
+    if a.ndim != 4 or a.shape[-1] != 4:
+        raise ValueError(f"expected [n, rows, W, 4] images, got {a.shape}")
+    n, rows, w, _ = a.shape
+    if accum is None:
+        accum = _aligned_rows(rows, 8 * w).view(np.uint16).reshape(rows, w, 4)
+    if accum.dtype != np.uint16 or accum.shape != (rows, w, 4) or accum.strides[1:] != (8, 2):
+        raise ValueError(f"expected a uint16 [{rows}, {w}, 4] accumulator with dense pixels")
+    if rows and w:
+        check(load().sr_accum_add(a.ctypes.data, 4 * w, 4 * w * rows, n, w, rows, 1 if reset else 0, accum.ctypes.data,
+                                  accum.strides[0], 0, None), "sr_accum_add")
+    return accum
+
+
+def accum_resolve(accum, n: int):
+    """sr_accum_resolve's host form: a uint16 accumulator [rows, W, 4] of n
+    images (host array) -> the uint8 frame [rows, W, 4]."""
+    import numpy as np
+
+    a = np.asarray(accum)
+    if a.dtype != np.uint16 or a.ndim != 3 or a.shape[2] != 4 or a.strides[1:] != (8, 2):
+        raise ValueError(f"expected a uint16 [rows, W, 4] accumulator with dense pixels, got {a.dtype} {a.shape}")
+    rows, w, _ = a.shape
+    out = np.empty((rows, w, 4), dtype=np.uint8)
+    if rows and w:
+        check(load().sr_accum_resolve(a.ctypes.data, a.strides[0], w, rows, int(n), out.ctypes.data, 4 * w, 0, None),
+              "sr_accum_resolve")
     return out
 
 

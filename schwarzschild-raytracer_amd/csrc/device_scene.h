@@ -213,6 +213,9 @@ typedef struct {
     float pos[3];
     float axes[9];
     float ray_forward;  // 1 / tan(fov/360*PI), computed once on the host (frag:859)
+    // the frame's sample phase (sr.h "Sample phases"): its pixels' offset in
+    // the cells of the launch's uv grid, 0 .. sr_dev_frame.grid - 1
+    int32_t sub_x, sub_y;
 } sr_dev_cam;
 
 // Frames one launch renders (sr_render_blocks_batch): the same rows of
@@ -238,6 +241,12 @@ typedef struct {
     int32_t filter_mode;
     int32_t cull;       // segment culling on/off (off = the reference's exhaustive loop)
     int32_t width, height;
+    // the uv grid (geodesic.hip sample_uv): output pixel (x, y) of frame f is
+    // pixel (grid x + cam[f].sub_x, grid y + cam[f].sub_y) of the uv_width x
+    // uv_height = (grid width) x (grid height) frame, whose size res_x, res_y
+    // are. A plain launch: grid 1, offsets 0.
+    int32_t grid;
+    int32_t uv_width, uv_height;
     // output row mapping: output row k renders frame row
     //   y = row_base + (k / block_rows) * block_stride + (k % block_rows)
     int32_t nrows;

@@ -2367,11 +2367,21 @@ struct PS {
     }
 };
 
+// full_screen_quad.vert:7-10: uv = NDC of the pixel centre. The pixel is the
+// one of the frame's uv grid (sr.h "Sample phases"): output pixel (px, py) of
+// a phase launch is sample (grid px + sub_x, grid py + sub_y) of the (grid
+// width) x (grid height) sample frame, and uv has that frame's own
+// expressions on the same integers. A plain launch is grid 1, offset 0.
+__device__ __forceinline__ f2 sample_uv(const sr_dev_frame& fr, const sr_dev_cam& cam, const Pix& q) {
+    const int sx = fr.grid * q.px + cam.sub_x, sy = fr.grid * q.py + cam.sub_y;
+    return F2((float)(2 * sx + 1) / (float)fr.uv_width - 1.0f, (float)(2 * sy + 1) / (float)fr.uv_height - 1.0f);
+}
+
 // frag:845-857: the crosshair's initial FragColor
-__device__ __forceinline__ f4 crosshair_frag(const sr_dev_frame& fr, const Pix& q) {
+__device__ __forceinline__ f4 crosshair_frag(const sr_dev_frame& fr, const sr_dev_cam& cam, const Pix& q) {
     f4 frag = F4(0.0f, 0.0f, 0.0f, 0.0f);
     if (fr.crosshair) {
-        f2 uv = F2((float)(2 * q.px + 1) / (float)fr.width - 1.0f, (float)(2 * q.py + 1) / (float)fr.height - 1.0f);
+        f2 uv = sample_uv(fr, cam, q);
         float hx = fabsf(uv.x * fr.res_x / 2.0f), hy = fabsf(uv.y * fr.res_y / 2.0f);
         if ((hx < 1.0f && hy > 5.0f && hy < 15.0f) || (hy < 1.0f && hx > 5.0f && hx < 15.0f))
             frag = F4(0.5f, 0.5f, 0.5f, 0.5f);
@@ -2385,8 +2395,7 @@ __device__ __forceinline__ f4 crosshair_frag(const sr_dev_frame& fr, const Pix& 
 // the same expressions on the camera position, once per frame)
 __device__ __forceinline__ int init_pixel(const sr_dev_frame& fr, const sr_dev_cam& cam, const sr_dev_start& st,
                                           const Pix& q, Ray& r) {
-    // full_screen_quad.vert:7-10: uv = NDC of the pixel centre
-    f2 uv = F2((float)(2 * q.px + 1) / (float)fr.width - 1.0f, (float)(2 * q.py + 1) / (float)fr.height - 1.0f);
+    f2 uv = sample_uv(fr, cam, q);
     f2 uvv = F2(uv.x, uv.y * fr.res_y / fr.res_x);
     m3 axes = ldm(cam.axes);
     r.ro = ld3(cam.pos);
@@ -3414,7 +3423,7 @@ __global__ __launch_bounds__(256, SR_SHADE_WAVES_PER_EU) void sr_shade_kernel(co
     const float4 rec = ps.get_rec(id);
     const int w0 = __float_as_int(rec.x);
     const int st = w0 & 7, nh = min((w0 >> 3) & 7, SR_PS_HITS);  // <= SR_PS_HITS written (memory safety)
-    f4 frag = crosshair_frag(fr, q);
+    f4 frag = crosshair_frag(fr, fr.cam[f], q);
     bool done = false;
     int steps_at = -1;
     for (int j = 0; j < nh && !done; j++) {  // frag:930-932 for each recorded hit, in order

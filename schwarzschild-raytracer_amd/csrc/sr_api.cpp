@@ -854,6 +854,7 @@ void build_cam(const sr_camera* cam, sr_dev_cam& dc) {
     std::memcpy(dc.pos, cam->transform.pos, sizeof dc.pos);
     std::memcpy(dc.axes, cam->transform.axes, sizeof dc.axes);
     dc.ray_forward = 1.0f / (float)std::tan((double)(cam->fov / 360.0f * kPi));
+    dc.sub_x = dc.sub_y = 0;  // launch() sets a phase launch's
 }
 
 // The orbital-plane exclusion of a budgeted cylinder (geodesic.hip SR_XCYL)
@@ -972,6 +973,9 @@ int build_frame(sr_ctx* ctx, const sr_camera* cam, const sr_params* p, int width
     fr.cull = ctx->cull ? 1 : 0;
     fr.width = width;
     fr.height = height;
+    fr.grid = 1;  // launch() sets a phase launch's uv grid
+    fr.uv_width = width;
+    fr.uv_height = height;
     fr.bg_w = ctx->bg_w;
     fr.bg_h = ctx->bg_h;
     fr.arr_w = ctx->arr_w;
@@ -1014,11 +1018,15 @@ int enter_stream(sr_ctx* ctx, hipStream_t s) {
 // frame (sr_render_adaptive): the integrate and shade kernels run the tiles
 // of this device list of launch codes (one entry per tile of the grid, -1 =
 // none); no order of the grid's shape is looked up, learned or updated, and
-// split tiles do not apply to it.
+// split tiles do not apply to it. phases (n_frames byte pairs {x, y}, each in
+// 0 .. grid - 1): a phase launch (sr.h "Sample phases"): every frame has the
+// camera cams[0], frame f is phase (phases[2 f], phases[2 f + 1]) of the grid
+// x grid sample grid; width, height and the rows are the output frame's.
 int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* params, int width, int height,
            int nrows, int row_base, int block_rows, int block_stride, uint8_t* out, size_t pitch,
            size_t frame_stride, float* dbg_rgba, int32_t* dbg_steps, sr_stream stream,
-           const int* d_block_list = nullptr, int32_t* d_wave_cost = nullptr, int* d_codes = nullptr) {
+           const int* d_block_list = nullptr, int32_t* d_wave_cost = nullptr, int* d_codes = nullptr, int grid = 1,
+           const uint8_t* phases = nullptr) {
     if (!ctx) return SR_E_INVALID;
     if (!ctx->scene_set) return SR_E_NOT_READY;
     if (!cams || n_frames < 1) return SR_E_INVALID;
@@ -1026,8 +1034,22 @@ int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* pa
     sr_dev_frame fr;
     int rc = build_frame(ctx, cams, params, width, height, fr);
     if (rc != SR_OK) return rc;
-    for (int f = 1; f < n_frames; f++) build_cam(&cams[f], fr.cam[f]);
+    for (int f = 1; f < n_frames; f++) build_cam(phases ? cams : &cams[f], fr.cam[f]);
     fr.batch = n_frames;
+    if (phases) {
+        if (grid < 1 || grid > SR_MAX_SUPERSAMPLE || width > INT32_MAX / (2 * grid) || height > INT32_MAX / (2 * grid))
+            return SR_E_INVALID;
+        for (int f = 0; f < n_frames; f++) {
+            if (phases[2 * f] >= grid || phases[2 * f + 1] >= grid) return SR_E_INVALID;
+            fr.cam[f].sub_x = phases[2 * f];
+            fr.cam[f].sub_y = phases[2 * f + 1];
+        }
+        fr.grid = grid;
+        fr.uv_width = grid * width;
+        fr.uv_height = grid * height;
+        fr.res_x = (float)fr.uv_width;  // the sample frame's resolution uniform
+        fr.res_y = (float)fr.uv_height;
+    }
     // the black hole's u window (geodesic.hip SR_BH_WINDOW): chord origins within r = 100
     fr.num_budget = ctx->h_scene.num_budget;
     fr.num_budget_cyl = __builtin_popcount((unsigned)ctx->h_scene.budget_cyl_mask);
@@ -1112,6 +1134,17 @@ extern "C" hipError_t sr_resolve_box_device(const uint8_t* samples, size_t sampl
 extern "C" void sr_resolve_box_host(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride, int width,
                                     int rows, int ss, uint8_t* out, size_t pitch, size_t out_frame_stride,
                                     int n_frames);
+
+// accum.hip
+extern "C" hipError_t sr_accum_add_device(const uint8_t* images, size_t pitch, size_t image_stride, int n_images,
+                                          int width, int rows, int reset, uint16_t* accum, size_t accum_pitch,
+                                          hipStream_t stream);
+extern "C" hipError_t sr_accum_resolve_device(const uint16_t* accum, size_t accum_pitch, int width, int rows, int n,
+                                              uint8_t* out, size_t pitch, hipStream_t stream);
+extern "C" void sr_accum_add_host(const uint8_t* images, size_t pitch, size_t image_stride, int n_images, int width,
+                                  int rows, int reset, uint16_t* accum, size_t accum_pitch);
+extern "C" void sr_accum_resolve_host(const uint16_t* accum, size_t accum_pitch, int width, int rows, int n,
+                                      uint8_t* out, size_t pitch);
 
 // adaptive.hip
 extern "C" hipError_t sr_edge_tiles_device(const uint8_t* img, size_t pitch, int width, int height, int threshold,
@@ -1699,6 +1732,98 @@ int sr_render_block_list_ss(sr_ctx* c, const sr_camera* cams, int n_frames, cons
     rc = ensure_block_list(c, blocks, n_blocks, reinterpret_cast<hipStream_t>(stream), &d);
     if (rc != SR_OK) return rc;
     return launch_ss(c, cams, n_frames, p, width, height, rows, 0, block_rows, d, ss, out, pitch, frame_stride, stream);
+}
+
+// ---- sample phases: a launch of the output frame's own shape (grid, pixel
+// state, launch order) whose pixels are one sub-sample position of the sample
+// frame (launch()'s `phases`), and the 16-bit accumulator that sums them
+// (accum.hip)
+
+static bool bad_grid(int ss) { return ss < 1 || ss > SR_MAX_SUPERSAMPLE; }
+
+int sr_render_phase(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int row_begin,
+                    int row_end, int ss, int phase_x, int phase_y, uint8_t* out, size_t pitch, sr_stream stream) {
+    if (bad_grid(ss) || phase_x < 0 || phase_x >= ss || phase_y < 0 || phase_y >= ss) return SR_E_INVALID;
+    if (!out || row_begin < 0 || row_end > height || row_begin > row_end) return SR_E_INVALID;
+    const int n = row_end - row_begin;
+    const uint8_t phase[2] = {(uint8_t)phase_x, (uint8_t)phase_y};
+    return launch(c, cam, 1, p, width, height, n, row_begin, n > 0 ? n : 1, 0, out, pitch, 0, nullptr, nullptr, stream,
+                  nullptr, nullptr, nullptr, ss, phase);
+}
+
+int sr_render_accumulate(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int row_begin,
+                         int row_end, int ss, const uint8_t* phases, int n_phases, int reset, uint16_t* accum,
+                         size_t accum_pitch, sr_stream stream) {
+    if (bad_grid(ss) || !phases || !accum || n_phases < 1) return SR_E_INVALID;
+    if (n_phases > SR_MAX_BATCH) return SR_E_CAPACITY;
+    for (int f = 0; f < 2 * n_phases; f++)
+        if (phases[f] >= ss) return SR_E_INVALID;
+    if (row_begin < 0 || row_end > height || row_begin > row_end) return SR_E_INVALID;
+    int rc = check_frames(c, cam, 1, p, width, height);
+    if (rc != SR_OK) return rc;
+    if (width > INT32_MAX / 8 || accum_pitch < (size_t)width * 8 || (((uintptr_t)accum | accum_pitch) & 7) != 0)
+        return SR_E_INVALID;
+    const int n = row_end - row_begin;
+    if (n == 0) return SR_OK;  // no rows: nothing is written
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    const size_t ipitch = (size_t)width * 4, istride = ipitch * (size_t)n;
+    rc = ensure_sample_scratch(c, istride * (size_t)n_phases, s);
+    if (rc != SR_OK) return rc;
+    rc = launch(c, cam, n_phases, p, width, height, n, row_begin, n, 0, c->d_ss, ipitch, istride, nullptr, nullptr,
+                stream, nullptr, nullptr, nullptr, ss, phases);
+    if (rc != SR_OK) return rc;
+    hipError_t e = sr_accum_add_device(c->d_ss, ipitch, istride, n_phases, width, n, reset ? 1 : 0, accum, accum_pitch, s);
+    // again at the end of the whole: a launch on another stream waits for the add too
+    if (hip_ok(e)) e = hipEventRecord(c->order_ev, s);
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
+}
+
+int sr_accum_add(const uint8_t* images, size_t pitch, size_t image_stride, int n_images, int width, int rows, int reset,
+                 uint16_t* accum, size_t accum_pitch, int on_device, sr_stream stream) {
+    if (!images || !accum || width <= 0 || rows < 0 || n_images < 1 || n_images > SR_MAX_ACCUM_PASSES)
+        return SR_E_INVALID;
+    if (width > INT32_MAX / 8 || pitch < (size_t)width * 4 || accum_pitch < (size_t)width * 8) return SR_E_INVALID;
+    if (n_images > 1 && image_stride < pitch * (size_t)rows) return SR_E_INVALID;
+    if ((((uintptr_t)images | pitch | (n_images > 1 ? image_stride : 0)) & 3) != 0) return SR_E_INVALID;
+    if ((((uintptr_t)accum | accum_pitch) & 7) != 0) return SR_E_INVALID;
+    if (!on_device) {
+        sr_accum_add_host(images, pitch, image_stride, n_images, width, rows, reset ? 1 : 0, accum, accum_pitch);
+        return SR_OK;
+    }
+    const hipError_t e = sr_accum_add_device(images, pitch, image_stride, n_images, width, rows, reset ? 1 : 0, accum,
+                                             accum_pitch, reinterpret_cast<hipStream_t>(stream));
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
+}
+
+int sr_accum_resolve(const uint16_t* accum, size_t accum_pitch, int width, int rows, int n, uint8_t* out, size_t pitch,
+                     int on_device, sr_stream stream) {
+    if (!accum || !out || width <= 0 || rows < 0 || n < 1 || n > SR_MAX_ACCUM_PASSES) return SR_E_INVALID;
+    if (width > INT32_MAX / 8 || pitch < (size_t)width * 4 || accum_pitch < (size_t)width * 8) return SR_E_INVALID;
+    if ((((uintptr_t)accum | accum_pitch) & 7) != 0 || (((uintptr_t)out | pitch) & 3) != 0) return SR_E_INVALID;
+    if (!on_device) {
+        sr_accum_resolve_host(accum, accum_pitch, width, rows, n, out, pitch);
+        return SR_OK;
+    }
+    const hipError_t e =
+        sr_accum_resolve_device(accum, accum_pitch, width, rows, n, out, pitch, reinterpret_cast<hipStream_t>(stream));
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
+}
+
+int sr_phase_order(int ss, int k, int* phase_x, int* phase_y) {
+    // ss 2, 4: the 2x2 and 4x4 ordered-dither matrices read by rank; ss 3:
+    // the centre, the diagonal, the other corners, then the edge midpoints
+    static const uint8_t order1[1][2] = {{0, 0}};
+    static const uint8_t order2[4][2] = {{0, 0}, {1, 1}, {1, 0}, {0, 1}};
+    static const uint8_t order3[9][2] = {{1, 1}, {0, 0}, {2, 2}, {2, 0}, {0, 2}, {1, 0}, {1, 2}, {0, 1}, {2, 1}};
+    static const uint8_t order4[16][2] = {{0, 0}, {2, 2}, {2, 0}, {0, 2}, {1, 1}, {3, 3}, {3, 1}, {1, 3},
+                                          {1, 0}, {3, 2}, {3, 0}, {1, 2}, {0, 1}, {2, 3}, {2, 1}, {0, 3}};
+    static const uint8_t(*const orders[4])[2] = {order1, order2, order3, order4};
+    if (bad_grid(ss) || k < 0 || k >= ss * ss || !phase_x || !phase_y) return SR_E_INVALID;
+    *phase_x = orders[ss - 1][k][0];
+    *phase_y = orders[ss - 1][k][1];
+    return SR_OK;
 }
 
 // ---- adaptive supersampling: the plain frame P into the caller's buffer,

@@ -221,6 +221,103 @@ class Renderer:
         )
         return out
 
+    def render_phase(self, cam: abi.Camera, params: abi.Params, width: int, height: int, ss: int, phase_x: int,
+                     phase_y: int, row_begin: int = 0, row_end: int | None = None, out=None, stream=None):
+        """One sub-sample position of every pixel (sr_render_phase): rows
+        [row_begin, row_end) of phase (phase_x, phase_y) of the ss x ss grid,
+        S[ss * y + phase_y][ss * x + phase_x] of the sample frame -> [rows, width, 4]."""
+        row_end = height if row_end is None else row_end
+        rows = row_end - row_begin
+        if out is None:
+            out = self.torch.empty((max(rows, 0), width, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and out.numel() >= rows * width * 4
+        abi.check(
+            self.lib.sr_render_phase(self.ctx, C.byref(cam), C.byref(params), width, height, row_begin, row_end,
+                                     int(ss), int(phase_x), int(phase_y), C.c_void_p(out.data_ptr()), width * 4,
+                                     self._stream(stream)),
+            "sr_render_phase",
+        )
+        return out
+
+    def new_accum(self, width: int, rows: int):
+        """A zeroed accumulator for render_accumulate / accum_add: int16 [rows, width, 4]
+        on this device (torch has no uint16 arithmetic; the bits are the ABI's uint16)."""
+        return self.torch.zeros((rows, width, 4), dtype=self.torch.int16, device=self.tdev)
+
+    def _check_accum(self, accum):
+        assert accum.dtype == self.torch.int16 and accum.dim() == 3 and accum.shape[2] == 4 and accum.is_contiguous()
+        return int(accum.shape[0]), int(accum.shape[1])
+
+    def render_accumulate(self, cam: abi.Camera, params: abi.Params, width: int, height: int, ss: int, phases,
+                          accum=None, reset: bool = False, row_begin: int = 0, row_end: int | None = None,
+                          stream=None):
+        """sr_render_accumulate: the phases [(x, y), ...] (at most abi.MAX_BATCH)
+        of the ss x ss grid in one launch, added to `accum` (new_accum; a new
+        one when None), or stored over it when reset -> accum."""
+        row_end = height if row_end is None else row_end
+        rows = row_end - row_begin
+        if accum is None:
+            accum, reset = self.new_accum(width, max(rows, 0)), True
+        assert self._check_accum(accum) == (max(rows, 0), width)
+        flat = [int(v) for ph in phases for v in ph]
+        arr = (C.c_uint8 * max(1, len(flat)))(*flat)
+        abi.check(
+            self.lib.sr_render_accumulate(self.ctx, C.byref(cam), C.byref(params), width, height, row_begin, row_end,
+                                          int(ss), arr, len(flat) // 2, 1 if reset else 0,
+                                          C.c_void_p(accum.data_ptr()), width * 8, self._stream(stream)),
+            "sr_render_accumulate",
+        )
+        return accum
+
+    def accum_add(self, images, accum=None, reset: bool = False, stream=None):
+        """sr_accum_add on the device: uint8 images [n, rows, W, 4] (or one
+        [rows, W, 4]) on this device added to `accum` (a new one when None) -> accum."""
+        if images.dim() == 3:
+            images = images[None]
+        assert images.dtype == self.torch.uint8 and images.dim() == 4 and images.shape[3] == 4 and images.is_contiguous()
+        n, rows, w = (int(v) for v in images.shape[:3])
+        if accum is None:
+            accum, reset = self.new_accum(w, rows), True
+        assert self._check_accum(accum) == (rows, w)
+        abi.check(
+            self.lib.sr_accum_add(C.c_void_p(images.data_ptr()), 4 * w, 4 * w * rows, n, w, rows, 1 if reset else 0,
+                                  C.c_void_p(accum.data_ptr()), 8 * w, 1, self._stream(stream)),
+            "sr_accum_add",
+        )
+        return accum
+
+    def accum_resolve(self, accum, n: int, out=None, stream=None):
+        """sr_accum_resolve on the device: min(255, (accum + n // 2) // n) of an
+        accumulator of n images -> uint8 [rows, W, 4]."""
+        rows, w = self._check_accum(accum)
+        if out is None:
+            out = self.torch.empty((rows, w, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and out.numel() >= rows * w * 4
+        abi.check(
+            self.lib.sr_accum_resolve(C.c_void_p(accum.data_ptr()), 8 * w, w, rows, int(n), C.c_void_p(out.data_ptr()),
+                                      4 * w, 1, self._stream(stream)),
+            "sr_accum_resolve",
+        )
+        return out
+
+    def progressive(self, cam: abi.Camera, params: abi.Params, width: int, height: int, ss: int,
+                    phases_per_launch: int = 1, stream=None):
+        """Progressive supersampling: renders the ss * ss phases in
+        abi.phase_order, phases_per_launch (1 .. abi.MAX_BATCH) per launch,
+        and yields (passes_done, frame) after each launch: the [height, width,
+        4] frame of the passes so far (a new tensor each time). The last one
+        equals render_ss's frame."""
+        order = abi.phase_order(ss)
+        if not 1 <= int(phases_per_launch) <= abi.MAX_BATCH:
+            raise ValueError(f"phases_per_launch must be in 1 .. {abi.MAX_BATCH}")
+        accum = self.new_accum(width, height)
+        done = 0
+        while done < len(order):
+            group = order[done:done + int(phases_per_launch)]
+            self.render_accumulate(cam, params, width, height, ss, group, accum=accum, reset=done == 0, stream=stream)
+            done += len(group)
+            yield done, self.accum_resolve(accum, done, stream=stream)
+
     def render_adaptive(self, cam: abi.Camera, params: abi.Params, width: int, height: int, ss: int, threshold: int,
                         grow: int = 0, out=None, stream=None):
         """The whole frame with ss x ss samples only in the 16x16 tiles that

@@ -9,6 +9,8 @@ hyperbolic trajectory (src/main.cpp:404-410) in batched launches.
   python tools/render.py --ssaa 2 --out frame_ss2.png      (2 x 2 samples per pixel, box resolve)
   python tools/render.py --ssaa 4 --adaptive 32 --grow 1 --out frame_a4.png
                                   (4 x 4 samples only in the 16x16 tiles with an edge above 32 levels)
+  python tools/render.py --progressive 4 --out pass_%02d.png
+                                  (progressive supersampling: the frame after each of the 16 passes)
 """
 import argparse
 import sys
@@ -38,7 +40,13 @@ def main():
                          "neighbouring pixels more than THRESHOLD levels apart in a channel (sr_render_adaptive)")
     ap.add_argument("--grow", type=int, default=0, choices=[0, 1, 2],
                     help="--adaptive: dilate the flagged tiles this many times by their 3x3 neighbourhood")
+    ap.add_argument("--progressive", type=int, default=None, choices=[1, 2, 3, 4], metavar="SS",
+                    help="progressive supersampling on an SS x SS grid (Renderer.progressive): one sample phase per "
+                         "launch in sr_phase_order, the frame so far written after each pass (--out with %%d for the "
+                         "pass number); the last one is --ssaa SS's frame")
     args = ap.parse_args()
+    if args.progressive is not None and (args.ssaa != 1 or args.adaptive is not None or args.flyby > 0):
+        ap.error("--progressive takes the grid itself: no --ssaa, --adaptive or --flyby")
     if args.adaptive is not None and (args.ssaa < 2 or args.flyby > 0):
         ap.error("--adaptive needs --ssaa 2 .. 4 and a single frame (no --flyby)")
     import torch
@@ -60,7 +68,13 @@ def main():
                                 raytrace_type=MODES[args.mode])
     params.crosshair = 1 if args.crosshair else 0
     W, H = args.width, args.height
-    if args.flyby <= 0:
+    if args.progressive is not None:
+        for k, frame in r.progressive(abi.default_camera(), params, W, H, args.progressive):
+            torch.cuda.synchronize()
+            path = args.out % k if "%" in args.out else f"{Path(args.out).stem}_{k:02d}.png"
+            abi.write_png(path, frame.cpu().numpy())
+            print(f"wrote {path} ({k} of {args.progressive ** 2} passes)")
+    elif args.flyby <= 0:
         if args.adaptive is not None:
             frame, tiles = r.render_adaptive(abi.default_camera(), params, W, H, args.ssaa, args.adaptive, args.grow)
             torch.cuda.synchronize()
