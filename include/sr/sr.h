@@ -320,7 +320,10 @@ int sr_render_block_list(sr_ctx* ctx, const sr_camera* cams, int n_frames, const
  * wave's longest ray's executed steps (a ray whose hit log filled counts with
  * the steps the resume kernel ran for it too) and [... + 1] = its budget events
  * (DESIGN.md §5): int32 [ceil(height / 8)][ceil(width / 8)][2]. Deterministic,
- * so every rank of a node derives the same block lists from it. */
+ * so every rank of a node derives the same block lists from it. The map comes
+ * from a culling kernel whatever the params: with max_revolutions <= 0 or a
+ * negative or NaN u_f, whose frames are rendered without culling (DESIGN.md
+ * §5), it is an estimate of their cost only. No pixel is written by this call. */
 int sr_wave_costs(sr_ctx* ctx, const sr_camera* cam, const sr_params* params, int width, int height,
                   int32_t* dev_out, sr_stream stream);
 

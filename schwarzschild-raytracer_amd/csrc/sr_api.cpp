@@ -971,6 +971,16 @@ int build_frame(sr_ctx* ctx, const sr_camera* cam, const sr_params* p, int width
     fr.crosshair = p->crosshair;
     fr.filter_mode = p->filter_mode;
     fr.cull = ctx->cull ? 1 : 0;
+    // The margins' premises about the parameters. A positive
+    // step angle: "outward" (du < 0, geodesic.hip integrate) means u falls
+    // only when phi grows; with max_revolutions <= 0 such a lane approaches
+    // what outward_clear / outward_slot declared passed. u_f >= +0: the fast
+    // and the coasting loop find u < 0 through their lower bound ulo = u_f
+    // (a negative or NaN u_f lets u run on below 0), and win_ok below reads
+    // 1 / u_f <= 100 as "every chord starts within r = 100" (-0.0: -inf). The
+    // reference accepts all of these, so such a launch runs the reference's
+    // own loop, the culling-off instantiation.
+    if (!(p->max_revolutions > 0) || !(p->u_f >= 0.0f) || std::signbit(p->u_f)) fr.cull = 0;
     fr.width = width;
     fr.height = height;
     fr.grid = 1;  // launch() sets a phase launch's uv grid

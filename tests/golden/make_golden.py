@@ -22,6 +22,7 @@ goldens do not depend on a JPEG decoder. Run in the build container:
     python tests/golden/make_golden.py            # writes tests/golden/golden.npz
     python tests/golden/make_golden.py --set r2   # writes tests/golden/golden_r2.npz
     python tests/golden/make_golden.py --set r3   # writes tests/golden/golden_r3.npz (headline-size bands)
+    python tests/golden/make_golden.py --set r4   # writes tests/golden/golden_r4.npz (scene and view extremes)
 """
 from __future__ import annotations
 
@@ -494,6 +495,92 @@ def cases_r3():
     return out
 
 
+def cases_r4():
+    """Round-4 goldens (golden_r4.npz): the oracle's judges at the extremes.
+    (name, scene, camera, params, width, height, skybox, pinned):
+    tests/extreme_cases.py's primitives alone (every group but the non-finite
+    one, every schedule, 64x40, the 256x128 skybox of
+    tests/test_scene_extremes_cases.py) and tests/view_cases.py's cameras and
+    parameters on scenes.scene_default(False) (68x44, the 512x256 skybox).
+    pinned = False: the shader's result rests on an operation GLSL leaves
+    undefined (tests/test_oracle_golden_extremes.py EXCLUDED); such a frame
+    is stored apart ("excluded"), to show that it is far from the oracle's."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import extreme_cases as X
+    import view_cases as V
+
+    out = []
+    for c in X.CASES:
+        if c.group == "nonfinite":
+            continue
+        for schedule in c.schedules:
+            out.append((f"scene/{c.name}/{schedule}", X.build(PKG, c, "alone"), X.camera_of(PKG, c),
+                        X.params_of(PKG, c, schedule), X.W, X.H, (256, 128), True))
+    for c in V.CASES:
+        out.append((f"view/{c.name}", V.host_scene(PKG, "golden"), V.camera_of(PKG, c), V.params_of(PKG, c),
+                    c.size[0], c.size[1], (512, 256), c.pinned))
+    return out
+
+
+def write_npz(path, store):
+    """np.savez_compressed with fixed member dates and order: the same
+    arrays give the same bytes."""
+    import io
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key in sorted(store):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(store[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def main_r4(args, ss, out_path):
+    """Renders cases_r4 on SwiftShader, prints the oracle's distance from
+    every frame (the figures of tests/test_oracle_golden_extremes.py's
+    ALLOW and EXCLUDED tables) and stores them."""
+    oracle = srpkg.load_oracle()
+    arr = sc.default_texture_array()[0]
+    store = {"meta_renderer": np.frombuffer(ss.renderer.encode(), dtype=np.uint8),
+             "meta_skybox_shape_scene": np.array([128, 256], dtype=np.int32),
+             "meta_skybox_shape_view": np.array([256, 512], dtype=np.int32)}
+    groups, bound = {}, None  # frames of one kind and size are stored as one array (they share most of their sky)
+    for name, scene, cam, params, W, H, sky, pinned in cases_r4():
+        if args.only and name != args.only:
+            continue
+        if bound != sky:
+            bg = sc.skybox(*sky)
+            ss.set_textures(bg, arr)
+            tex = oracle.TextureSet(bg, arr)
+            bound = sky
+        img = ss.render(scene, cam, params, W, H)
+        st = ss.render(scene, cam, params, W, H, steps_variant=True)
+        steps = st[:, :, 0].astype(np.int32) + 256 * st[:, :, 1].astype(np.int32)
+        o8, _, osteps = oracle.render(scene, cam, params, W, H, tex)
+        d = np.abs(o8.astype(int) - img.astype(int)).max(-1)
+        # (the step map holds the count modulo 65536: two bytes of the colour)
+        print(f"{name:44s} {'pinned  ' if pinned else 'excluded'} >4: {int((d > 4).sum()):5d}  >2: {int((d > 2).sum()):5d}"
+              f"  max {int(d.max()):3d}  steps differ {int((steps != osteps % 65536).sum()):5d} of {d.size}", flush=True)
+        g = groups.setdefault(f"{name.split('/')[0] if pinned else 'excluded'}_{W}x{H}", {k: [] for k in ("names", "rgba8", "steps", "scene",
+                                                                                  "camera", "params")})
+        g["names"].append(name)
+        g["rgba8"].append(img)
+        g["steps"].append(steps.astype(np.uint16))
+        g["scene"].append(sc.struct_bytes(scene))
+        g["camera"].append(sc.struct_bytes(cam))
+        g["params"].append(sc.struct_bytes(params))
+    for key, g in groups.items():
+        store[f"{key}/cases"] = np.frombuffer("\n".join(g["names"]).encode(), dtype=np.uint8)
+        for k in ("rgba8", "steps", "scene", "camera", "params"):
+            store[f"{key}/{k}"] = np.stack(g[k])
+    store["meta_groups"] = np.frombuffer("\n".join(groups).encode(), dtype=np.uint8)
+    write_npz(out_path, store)
+    print("wrote", out_path, Path(out_path).stat().st_size, "bytes")
+
+
 def scene_for(kind, sizes, mx):
     if kind == "features":
         return sc.scene_features()
@@ -517,16 +604,19 @@ def texture_set(kind):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--set", choices=["r1", "r2", "r3"], default="r1",
+    ap.add_argument("--set", choices=["r1", "r2", "r3", "r4"], default="r1",
                     help="r1: golden.npz (round-1 cases); r2: golden_r2.npz (reseed, config 2, material flags); "
-                         "r3: golden_r3.npz (bands of the headline-size frames)")
+                         "r3: golden_r3.npz (bands of the headline-size frames); "
+                         "r4: golden_r4.npz (scene and view extremes)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
     args = ap.parse_args(argv)
     out_path = args.out or str(Path(__file__).resolve().parent / {"r1": "golden.npz", "r2": "golden_r2.npz",
-                                                                    "r3": "golden_r3.npz"}[args.set])
+                                                                    "r3": "golden_r3.npz", "r4": "golden_r4.npz"}[args.set])
     ss = SwiftShader()
     print("renderer:", ss.renderer)
+    if args.set == "r4":
+        return main_r4(args, ss, out_path)
     store = {"meta_renderer": np.frombuffer(ss.renderer.encode(), dtype=np.uint8),
              "meta_skybox_shape": np.array([SKYBOX_H, SKYBOX_W], dtype=np.int32)}
     names = []
