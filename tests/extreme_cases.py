@@ -352,6 +352,27 @@ CASES = [
                                          "axes": (1.0, 0.0, 0.0, 0.0, NAN, 0.0, 0.0, 0.0, 1.0)}),
 ]
 
+# ---- one textured primitive of each type, filling a good part of a frame -------
+# tests/test_gpu_texel_edges.py's objects and camera; tests/shading_cases.py builds on them too, and
+# tests/golden/golden_r5.npz stores the scenes made from them (tests/test_oracle_golden_shading.py compares the bytes).
+TEXEL_CAMERA = ((0.0, 0.0, 12.0), (0.0, 0.0, 0.0), 60.0)
+TEXEL_FACING = axes_up((0.0, 0.0, 1.0))  # normal +z, columns x and -y
+TEXEL_OBJECTS = {
+    "sphere": {"type": "sphere", "pos": (0.0, 0.0, 6.0), "axes": axes_up((0.2, 1.0, 0.1)), "radius": 2.5},
+    "disk": {"type": "disk", "pos": (0.0, 0.0, 6.0), "axes": TEXEL_FACING, "radius": 3.0},
+    "annulus": {"type": "annulus", "pos": (0.0, 0.0, 6.0), "axes": TEXEL_FACING, "inner": 0.5, "outer": 3.0},
+    "cylinder": {"type": "cylinder", "pos": (0.0, -2.5, 6.0), "axes": axes_up((0.1, 1.0, 0.0)), "height": 5.0,
+                 "radius": 2.0},
+    "rectangle": {"type": "rectangle", "pos": (-3.0, 1.75, 6.0), "axes": TEXEL_FACING, "width": 6.0, "height": 3.5},
+    "box": {"type": "box", "pos": (-2.0, -2.0, 4.0), "axes": axes_up((0.3, 1.0, 0.2)), "width": 4.0, "depth": 4.0,
+            "height": 4.0},
+    "plane_patch": {"type": "plane", "pos": (0.0, 0.0, 6.0), "axes": TEXEL_FACING, "texture_offset": (-2.0, -1.5),
+                    "repeat_texture": 0, "texture_size": (4.0, 3.0)},
+    "plane_repeat": {"type": "plane", "pos": (0.0, 0.0, 6.0), "axes": TEXEL_FACING, "texture_offset": (-0.5, 0.25),
+                     "repeat_texture": 1, "texture_size": (3.0, 2.0)},
+}
+
+
 def cell_id(cell):
     c, host, schedule = cell
     return f"{c.name}-{host}-{schedule}"

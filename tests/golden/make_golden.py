@@ -23,6 +23,7 @@ goldens do not depend on a JPEG decoder. Run in the build container:
     python tests/golden/make_golden.py --set r2   # writes tests/golden/golden_r2.npz
     python tests/golden/make_golden.py --set r3   # writes tests/golden/golden_r3.npz (headline-size bands)
     python tests/golden/make_golden.py --set r4   # writes tests/golden/golden_r4.npz (scene and view extremes)
+    python tests/golden/make_golden.py --set r5   # writes tests/golden/golden_r5.npz (shading extremes)
 """
 from __future__ import annotations
 
@@ -581,6 +582,68 @@ def main_r4(args, ss, out_path):
     print("wrote", out_path, Path(out_path).stat().st_size, "bytes")
 
 
+def cases_r5():
+    """Round-5 goldens (golden_r5.npz): tests/shading_cases.py's cases that
+    fit the "features" capacity profile, alone, in every mode of the case, 65x41.
+    (name, scene, camera, params, texture key, pinned); pinned = False as in
+    cases_r4 (tests/test_oracle_golden_shading.py EXCLUDED)."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import shading_cases as S
+
+    return [(f"{c.name}/{mode}", S.build(PKG, c, "alone"), S.camera_of(PKG, c), S.params_of(PKG, c, mode), c.textures,
+             c.pin == "pin") for c in S.CASES if c.pin for mode in c.modes]
+
+
+def main_r5(args, ss, out_path):
+    """Renders cases_r5 on SwiftShader, prints the oracle's distance from
+    every frame (the figures of tests/test_oracle_golden_shading.py's ALLOW
+    and EXCLUDED tables) and stores them. The oracle samples with
+    SwiftShader's filter where the case samples a texture or a skybox of its
+    own (shading_cases.oracle_params_for_shader)."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import shading_cases as S
+
+    oracle = srpkg.load_oracle()
+    store = {"meta_renderer": np.frombuffer(ss.renderer.encode(), dtype=np.uint8)}
+    groups, bound = {}, None
+    for name, scene, cam, params, key, pinned in cases_r5():
+        if args.only and args.only not in name:
+            continue
+        if bound != key:
+            bg, arr, _ = S.textures_of(PKG, key)
+            ss.set_textures(bg, arr)
+            tex = oracle.TextureSet(bg, arr)
+            bound = key
+        img = ss.render(scene, cam, params, S.W, S.H, profile="features")
+        st = ss.render(scene, cam, params, S.W, S.H, steps_variant=True, profile="features")
+        steps = st[:, :, 0].astype(np.int32) + 256 * st[:, :, 1].astype(np.int32)
+        o8, _, osteps = oracle.render(scene, cam, S.oracle_params_for_shader(PKG, S.BY_NAME[name.split("/")[0]], params),
+                                      S.W, S.H, tex)
+        d = np.abs(o8.astype(int) - img.astype(int)).max(-1)
+        print(f"{name:52s} {'pinned  ' if pinned else 'excluded'} >4: {int((d > 4).sum()):5d}  >2: {int((d > 2).sum()):5d}"
+              f"  max {int(d.max()):3d}  steps differ {int((steps != osteps).sum()):5d} of {d.size}", flush=True)
+        g = groups.setdefault("pinned" if pinned else "excluded", {k: [] for k in ("names", "rgba8", "steps", "scene",
+                                                                                     "camera", "params")})
+        g["names"].append(name)
+        g["rgba8"].append(img)
+        g["steps"].append(steps.astype(np.uint8))  # (100 steps at the most)
+        g["scene"].append(sc.struct_bytes(scene))
+        g["camera"].append(sc.struct_bytes(cam))
+        g["params"].append(sc.struct_bytes(params))
+    for key, g in groups.items():
+        store[f"{key}/cases"] = np.frombuffer("\n".join(g["names"]).encode(), dtype=np.uint8)
+        for k in ("steps", "scene", "camera", "params"):
+            store[f"{key}/{k}"] = np.stack(g[k])
+        # The frames as channel planes of differences along x, modulo 256 (lossless: shading_cases.decode_frames
+        # sums them up again); these smooth frames of random texels deflate to half the size that way.
+        frames = np.stack(g["rgba8"])
+        store[f"{key}/rgba8_planes_dx"] = S.encode_frames(frames)
+        assert np.array_equal(S.decode_frames(store[f"{key}/rgba8_planes_dx"]), frames)
+    store["meta_groups"] = np.frombuffer("\n".join(groups).encode(), dtype=np.uint8)
+    write_npz(out_path, store)
+    print("wrote", out_path, Path(out_path).stat().st_size, "bytes")
+
+
 def scene_for(kind, sizes, mx):
     if kind == "features":
         return sc.scene_features()
@@ -604,19 +667,22 @@ def texture_set(kind):
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--set", choices=["r1", "r2", "r3", "r4"], default="r1",
+    ap.add_argument("--set", choices=["r1", "r2", "r3", "r4", "r5"], default="r1",
                     help="r1: golden.npz (round-1 cases); r2: golden_r2.npz (reseed, config 2, material flags); "
                          "r3: golden_r3.npz (bands of the headline-size frames); "
-                         "r4: golden_r4.npz (scene and view extremes)")
+                         "r4: golden_r4.npz (scene and view extremes); r5: golden_r5.npz (shading extremes)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default=None)
     args = ap.parse_args(argv)
     out_path = args.out or str(Path(__file__).resolve().parent / {"r1": "golden.npz", "r2": "golden_r2.npz",
-                                                                    "r3": "golden_r3.npz", "r4": "golden_r4.npz"}[args.set])
+                                                                    "r3": "golden_r3.npz", "r4": "golden_r4.npz",
+                                                                    "r5": "golden_r5.npz"}[args.set])
     ss = SwiftShader()
     print("renderer:", ss.renderer)
     if args.set == "r4":
         return main_r4(args, ss, out_path)
+    if args.set == "r5":
+        return main_r5(args, ss, out_path)
     store = {"meta_renderer": np.frombuffer(ss.renderer.encode(), dtype=np.uint8),
              "meta_skybox_shape": np.array([SKYBOX_H, SKYBOX_W], dtype=np.int32)}
     names = []

@@ -50,22 +50,7 @@ TEXTURE_INDICES = [0, 1, 2, 11]
 UV_FLAGS = [(0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 1)]  # swap_uvs, invert_uv_x, invert_uv_y
 COMBOS = [(t, f) for t in TEXTURE_INDICES for f in UV_FLAGS]
 
-CAMERA = ((0.0, 0.0, 12.0), (0.0, 0.0, 0.0), 60.0)
-FACING = X.axes_up((0.0, 0.0, 1.0))  # normal +z, columns x and -y
-OBJECTS = {
-    "sphere": {"type": "sphere", "pos": (0.0, 0.0, 6.0), "axes": X.axes_up((0.2, 1.0, 0.1)), "radius": 2.5},
-    "disk": {"type": "disk", "pos": (0.0, 0.0, 6.0), "axes": FACING, "radius": 3.0},
-    "annulus": {"type": "annulus", "pos": (0.0, 0.0, 6.0), "axes": FACING, "inner": 0.5, "outer": 3.0},
-    "cylinder": {"type": "cylinder", "pos": (0.0, -2.5, 6.0), "axes": X.axes_up((0.1, 1.0, 0.0)), "height": 5.0,
-                 "radius": 2.0},
-    "rectangle": {"type": "rectangle", "pos": (-3.0, 1.75, 6.0), "axes": FACING, "width": 6.0, "height": 3.5},
-    "box": {"type": "box", "pos": (-2.0, -2.0, 4.0), "axes": X.axes_up((0.3, 1.0, 0.2)), "width": 4.0, "depth": 4.0,
-            "height": 4.0},
-    "plane_patch": {"type": "plane", "pos": (0.0, 0.0, 6.0), "axes": FACING, "texture_offset": (-2.0, -1.5),
-                    "repeat_texture": 0, "texture_size": (4.0, 3.0)},
-    "plane_repeat": {"type": "plane", "pos": (0.0, 0.0, 6.0), "axes": FACING, "texture_offset": (-0.5, 0.25),
-                     "repeat_texture": 1, "texture_size": (3.0, 2.0)},
-}
+CAMERA, FACING, OBJECTS = X.TEXEL_CAMERA, X.TEXEL_FACING, X.TEXEL_OBJECTS
 NON_VACUOUS = ("rectangle", "sphere")
 
 
