@@ -578,6 +578,94 @@ int sr_render_debug(sr_ctx* ctx, const sr_camera* cam, const sr_params* params, 
                     int height, int row_begin, int row_end, float* dev_rgba32,
                     uint8_t* dev_rgba8, int32_t* dev_steps, sr_stream stream);
 
+/* ---- Retained frames (not in the reference, which walks every geodesic again
+ * for every draw). A launch leaves a record per pixel: how the ray ended, its
+ * final direction, its logged hits (point, object, step count) and, where the
+ * log filled, the state to resume from. The record depends on the geometry,
+ * the camera, the params, the test ray and the hits' opacity only; lights,
+ * Phong terms, a colour's rgb, normal maps and the skybox never reach the
+ * integrate kernel. The context remembers what its pixel state holds, the
+ * retained frame, and for how long it stays true.
+ *
+ * A retained frame exists after a successful sr_render, sr_render_blocks,
+ * sr_render_blocks_batch, sr_render_block_list, sr_render_debug,
+ * sr_render_phase, sr_render_ss or sr_render_block_list_ss of at least one
+ * row. It does not exist before the first launch, after sr_render_adaptive
+ * (its sparse sample launch overwrote the plain frame's rays), after
+ * sr_render_accumulate or sr_wave_costs, or after a launch of zero rows. A
+ * later launch of any kind replaces it.
+ *  - sr_set_background keeps it (a reshade reads the current image and size);
+ *  - sr_set_texture_array and sr_set_test_ray drop it;
+ *  - sr_set_scene keeps it when the new scene differs from the context's
+ *    current one in shading-only fields at most (sr_scene_shading_only), and
+ *    drops it otherwise; the call itself behaves the same in both cases;
+ *  - sr_set_split, sr_set_latency_mode and culling do not matter to it.
+ *
+ * Shading-only fields, compared as bytes (a NaN equals itself): num_lights
+ * and all of lights[]; per material color[0..2], ambient, diffuse, specular,
+ * shininess and normal_map_index. Everything else is geometry: objects, every
+ * primitive array, planes, materials[].color[3] (opacity), texture_index,
+ * invert_uv_x / invert_uv_y / swap_uvs, double_sided_normals, flip_normals,
+ * texture_sizes and max_texture_size; a difference there drops the frame even
+ * in a material no object uses.
+ *
+ * Reshade. Definition: sr_reshade writes exactly the bytes the retained call
+ * would write if it were issued again now with its own cameras, params and
+ * arguments, with the context's current scene, background and texture array.
+ * By that definition:
+ *  - the rows, layout, batch, block list and the -1 padding and rows past the
+ *    frame's end left unwritten are the retained launch's; the pitch and frame
+ *    stride are this call's, under the retained call's rules;
+ *  - a retained supersampled launch is shaded into the context's sample
+ *    scratch and box-resolved into the caller's buffer;
+ *  - the retained frame stays valid: reshade any number of times;
+ *  - sr_diag_counters()[0] stays 0: a shading-only change cannot turn an
+ *    opaque-classified hit translucent.
+ * Asynchronous on `stream`, no host wait, ordered like every launch of the
+ * context; the geodesics are not walked again (the shade and resume kernels
+ * only) and no launch order is learned or touched. */
+
+/* 1 when b differs from a in shading-only fields at most, 0 otherwise (null: 0) */
+int sr_scene_shading_only(const sr_scene* a, const sr_scene* b);
+/* 1 when the context holds a retained frame that sr_reshade would accept */
+int sr_can_reshade(sr_ctx* ctx);
+
+/* SR_E_NOT_READY without a valid retained frame; SR_E_INVALID for a null
+ * output, pitch_bytes < 4 * width or, for a batch, frame_stride_bytes <
+ * pitch_bytes * rows. Nothing is written in any error case. */
+int sr_reshade(sr_ctx* ctx, uint8_t* dev_rgba8, size_t pitch_bytes, size_t frame_stride_bytes, sr_stream stream);
+
+/* The sr_render_debug form (float FragColor, RGBA8, step counts; dense rows,
+ * each may be NULL but not all) of a retained launch of one frame that was
+ * not supersampled; SR_E_INVALID otherwise. */
+int sr_reshade_debug(sr_ctx* ctx, float* dev_rgba32, uint8_t* dev_rgba8, int32_t* dev_steps, sr_stream stream);
+
+/* Pick. "Which object is under this pixel?" has no straight-ray answer here:
+ * light bends, only the retained rays know. Definition: sr_pick_map writes,
+ * for every pixel of the retained launch, the code of the first surface on
+ * the pixel's ray, in the shader's own walk (frag:930-932; visiting order and
+ * strict < as intersect()), that is not a single-sided surface seen from
+ * behind (such a surface adds vec4(0) and the ray goes on): the index into
+ * scene.objects[], or one of the negative codes below. By that definition:
+ *  - a translucent front surface is reported, not what shows through it;
+ *  - the flat part of a ray (flat and split modes, radial rays, the tail
+ *    beyond 1 / u_f, every escaping ray while the overlay is visible) is the
+ *    one unbounded intersect: its closest hit, or SR_PICK_SKY when that is a
+ *    back face of a single-sided material (the shader does not look behind);
+ *  - the map does not depend on shading-only fields or on reshades in between.
+ * One int32 per pixel, rows, layout, batch, block lists and unwritten padding
+ * as the retained launch's; dev_ids and pitch_bytes multiples of 4,
+ * pitch_bytes >= 4 * width (SR_E_INVALID; for a batch also a stride below
+ * pitch_bytes * rows or no multiple of 4). SR_E_NOT_READY without a retained
+ * frame and for a retained supersampled launch: the picking surface is the
+ * plain frame. Asynchronous on `stream`. */
+#define SR_PICK_SKY             (-1)  /* the ray ends in the background */
+#define SR_PICK_HOLE            (-2)
+#define SR_PICK_TEST_RAY_FLAT   (-3)
+#define SR_PICK_TEST_RAY_CURVED (-4)
+#define SR_PICK_NONE            (-5)  /* no ray: a pixel the noise mask blacked out */
+int sr_pick_map(sr_ctx* ctx, int32_t* dev_ids, size_t pitch_bytes, size_t frame_stride_bytes, sr_stream stream);
+
 /* Split tiles (not in the reference; a latency knob, the pixels are unchanged):
  * the next frames run the max_tiles costliest 16x16 workgroup tiles of the
  * previous frame on this context whose longest ray took at least min_steps

@@ -215,7 +215,14 @@ SIGNATURES = {
     "sr_accum_add": (_i, [_p, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _p, C.c_size_t, _i, _p]),
     "sr_accum_resolve": (_i, [_p, C.c_size_t, _i, _i, _i, _p, C.c_size_t, _i, _p]),
     "sr_phase_order": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "sr_scene_shading_only": (_i, [C.POINTER(Scene), C.POINTER(Scene)]),
+    "sr_can_reshade": (_i, [_p]),
+    "sr_reshade": (_i, [_p, _p, C.c_size_t, C.c_size_t, _p]),
+    "sr_reshade_debug": (_i, [_p, _p, _p, _p, _p]),
+    "sr_pick_map": (_i, [_p, _p, C.c_size_t, C.c_size_t, _p]),
 }
+# sr_pick_map's codes below the indices into scene.objects[]
+PICK_SKY, PICK_HOLE, PICK_TEST_RAY_FLAT, PICK_TEST_RAY_CURVED, PICK_NONE = -1, -2, -3, -4, -5
 MAX_SUPERSAMPLE = 4
 MAX_BATCH = 32  # frames (cameras or phases) of one launch
 MAX_ACCUM_PASSES = 256
@@ -226,6 +233,7 @@ EXTRA_SIGNATURES = {
     "sr_debug_kernel_times": (_i, [_p, C.POINTER(C.c_float), _i, C.POINTER(_i)]),
     "sr_debug_last_order": (_i, [_p, C.POINTER(_i), _i, C.POINTER(_i)]),
     "sr_debug_pixel_state": (_i, [_p, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sr_debug_retained_shape": (_i, [_p, C.POINTER(_i)]),
 }
 
 _lib = None
@@ -376,6 +384,12 @@ def accum_resolve(accum, n: int):
         check(load().sr_accum_resolve(a.ctypes.data, a.strides[0], w, rows, int(n), out.ctypes.data, 4 * w, 0, None),
               "sr_accum_resolve")
     return out
+
+
+def scene_shading_only(a: Scene, b: Scene) -> bool:
+    """sr_scene_shading_only: b differs from a in lights and the materials'
+    rgb, Phong terms and normal maps at most (a retained frame outlives it)."""
+    return bool(load().sr_scene_shading_only(C.byref(a), C.byref(b)))
 
 
 def check_layout() -> dict:

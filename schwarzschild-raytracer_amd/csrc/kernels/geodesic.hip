@@ -3632,3 +3632,120 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
     if (ev4) (void)hipEventRecord(ev4[3], stream);
     return hipGetLastError();
 }
+
+// ---- retained frames (sr.h): the pixel state a launch left, shaded again or
+// read for the first surface of every ray
+
+// sr_reshade: the shade and resume kernels of sr_launch_geodesic alone, on
+// the pixel state its integrate kernel wrote. The resume counter, which that
+// kernel's first workgroup clears, is cleared on the stream here; the shade
+// kernel runs without an order (order_tiles does not run, no learned order
+// or cost is touched).
+extern "C" hipError_t sr_launch_reshade(const sr_dev_scene* sc, const float4* tbl, const float* segs,
+                                        const uint32_t* bg, const uint32_t* arr, const sr_dev_frame* fr, uint8_t* out,
+                                        size_t pitch, float* dbg_rgba, int32_t* dbg_steps, float* ps, size_t ps_n,
+                                        int* list, int* count, int* diag, hipStream_t stream) {
+    dim3 block(256);
+    dim3 grid((fr->width + 15) / 16, (fr->nrows + 15) / 16);
+    if (grid.x == 0 || grid.y == 0) return hipSuccess;
+    const unsigned nblocks = grid.x * grid.y;
+    const unsigned B = (unsigned)fr->batch;
+    if (B < 1 || B > SR_MAX_BATCH || fr->tiles != (int)nblocks) return hipErrorInvalidValue;
+    if ((size_t)nblocks * B * 256 > ps_n || (size_t)nblocks * B * 256 > (size_t)INT32_MAX) return hipErrorInvalidValue;
+    if (!ps || !list || !count || !diag || fr->wave_cost) return hipErrorInvalidValue;
+    const bool cull = fr->cull != 0;
+    const bool tr = cull && fr->tr_visible != 0;
+    const hipError_t e = hipMemsetAsync(count, 0, sizeof(int), stream);
+    if (e != hipSuccess) return e;
+    OrderArgs oa{nullptr, nullptr, (int)nblocks, fr->max_steps, 0, 6, fr->split_min_steps};
+    hipLaunchKernelGGL(sr_shade_kernel<false>, dim3(grid.x, grid.y * B), block, 0, stream, sc, segs, bg, arr, *fr, ps,
+                       ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa, (const int*)nullptr);
+    unsigned nb = (nblocks * B < SR_RESUME_TILES ? nblocks * B : SR_RESUME_TILES) * SR_WG_PER_TILE;
+    if (tr)
+        hipLaunchKernelGGL((sr_resume_kernel<true, true>), dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr,
+                           ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count);
+    else if (cull)
+        hipLaunchKernelGGL(sr_resume_kernel<true>, dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n,
+                           out, pitch, dbg_rgba, dbg_steps, list, count);
+    else
+        hipLaunchKernelGGL(sr_resume_kernel<false>, dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n,
+                           out, pitch, dbg_rgba, dbg_steps, list, count);
+    return hipGetLastError();
+}
+
+// sr_pick_map's codes (sr.h SR_PICK_*) for the slots of a Hit
+#define PICK_SKY (-1)
+#define PICK_NONE (-5)
+__device__ __forceinline__ int pick_code(int slot) {
+    // SLOT_BH -1, SLOT_TR_FLAT -2, SLOT_TR_CURVED -3 -> SR_PICK_HOLE -2, _TEST_RAY_FLAT -3, _TEST_RAY_CURVED -4
+    return slot >= 0 ? slot : slot >= SLOT_TR_CURVED ? slot - 1 : PICK_SKY;
+}
+
+// The flat part of a ray (ST_FLAT): the one unbounded intersect's closest
+// hit, unless it is a single-sided surface seen from behind (vec4(0): the
+// shader does not look behind it, the pixel is the background's). Behind a
+// noinline boundary, and a template like the kernel below: both are emitted
+// where sr_launch_pick instantiates them, after every frame kernel, whose
+// code and addresses in the code object stay the parent's.
+template <int V>
+__device__ __noinline__ int pick_flat(const sr_dev_scene* __restrict__ sc, const float* __restrict__ segs,
+                                      const sr_dev_frame& fr, f3 ro, f3 rd) {
+    const Hit h = closest_hit_all(sc, segs, ro, rd, -1.0f);
+    if (h.slot == SLOT_NONE) return PICK_SKY;
+    Tex tx;
+    tx.bg = nullptr;
+    tx.arr = nullptr;
+    tx.opq = nullptr;
+    return hit_opacity(sc, fr, tx, h, -rd, true) == OP_ZERO ? PICK_SKY : pick_code(h.slot);
+}
+
+// One lane per pixel id, the shade kernel's grid without the order row: 16x16
+// tiles over the batch. The first logged hit's slot (the log holds no surface
+// seen from behind: OP_ZERO hits are skipped by the step loop), else the ray's
+// end. Reads the 16-byte record, the first hit's first 16 bytes when there is
+// one and ro (12 bytes) of a flat ray; writes 4 bytes.
+template <int V = 0>
+__global__ __launch_bounds__(256) void sr_pick_kernel(const sr_dev_scene* __restrict__ sc,
+                                                      const float* __restrict__ segs, sr_dev_frame fr,
+                                                      const float* __restrict__ ps_base, size_t ps_n,
+                                                      int32_t* __restrict__ out, size_t pitch, size_t frame_stride) {
+    const int vblock = (int)blockIdx.y * gridDim.x + blockIdx.x;  // frame f's tiles are rows f*gy ..
+    const int f = vblock / fr.tiles, block = vblock - f * fr.tiles;
+    Pix q;
+    if (!pixel_of(fr, block, threadIdx.x, q)) return;
+    const size_t id = (size_t)vblock * 256 + threadIdx.x;
+    const float* const rp = ps_base + 4 * id;
+    const float4 rec = *reinterpret_cast<const float4*>(rp);
+    const int w0 = __float_as_int(rec.x);
+    const int st = w0 & 7, nh = (w0 >> 3) & 7;
+    int code = PICK_NONE;  // ST_DONE: no ray
+    if (nh > 0) {
+        const float4 a = *reinterpret_cast<const float4*>(ps_base + 4 * ps_n + id * 8);  // hit 0 (PS::hit)
+        code = pick_code(((__float_as_int(a.w) & 0xff) - PS_KEY_BIAS) >> 3);
+    } else if (st == ST_BH) {
+        code = pick_code(SLOT_BH);
+    } else if (st == ST_BG) {
+        code = PICK_SKY;
+    } else if (st == ST_FLAT) {
+        const size_t pl = (size_t)(PS_PLANES + PS_RO) * ps_n + id;  // PS::at
+        code = pick_flat<V>(sc, segs, fr, F3(ps_base[pl], ps_base[pl + ps_n], ps_base[pl + 2 * ps_n]),
+                         F3(rec.y, rec.z, rec.w));
+    }
+    char* const row = reinterpret_cast<char*>(out) + (size_t)f * frame_stride + (size_t)q.k * pitch;
+    *reinterpret_cast<int32_t*>(row + (size_t)q.px * 4) = code;
+}
+
+extern "C" hipError_t sr_launch_pick(const sr_dev_scene* sc, const float* segs, const sr_dev_frame* fr,
+                                     const float* ps, size_t ps_n, int32_t* out, size_t pitch, size_t frame_stride,
+                                     hipStream_t stream) {
+    dim3 grid((fr->width + 15) / 16, (fr->nrows + 15) / 16);
+    if (grid.x == 0 || grid.y == 0) return hipSuccess;
+    const unsigned nblocks = grid.x * grid.y;
+    const unsigned B = (unsigned)fr->batch;
+    if (B < 1 || B > SR_MAX_BATCH || fr->tiles != (int)nblocks) return hipErrorInvalidValue;
+    if ((size_t)nblocks * B * 256 > ps_n || (size_t)nblocks * B * 256 > (size_t)INT32_MAX) return hipErrorInvalidValue;
+    if (!ps || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sr_pick_kernel<0>, dim3(grid.x, grid.y * B), dim3(256), 0, stream, sc, segs, *fr, ps, ps_n, out,
+                       pitch, frame_stride);
+    return hipGetLastError();
+}

@@ -32,6 +32,19 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
                                          uint8_t* out, size_t pitch, float* dbg_rgba, int32_t* dbg_steps,
                                          float* ps, size_t ps_n, int* list, int* count, int* order, int* cost,
                                          int* diag, sr_dev_start* start, hipEvent_t* ev4, hipStream_t stream);
+extern "C" hipError_t sr_resolve_box_device(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride,
+                                            int width, int rows, int ss, const int* dev_blocks, int block_rows,
+                                            int height, uint8_t* out, size_t pitch, size_t out_frame_stride,
+                                            int n_frames, hipStream_t stream);
+// the shade and resume kernels alone, on pixel state a launch left (sr_reshade)
+extern "C" hipError_t sr_launch_reshade(const sr_dev_scene* sc, const float4* tbl, const float* segs,
+                                        const uint32_t* bg, const uint32_t* arr, const sr_dev_frame* fr, uint8_t* out,
+                                        size_t pitch, float* dbg_rgba, int32_t* dbg_steps, float* ps, size_t ps_n,
+                                        int* list, int* count, int* diag, hipStream_t stream);
+// one object code per pixel from that state (sr_pick_map)
+extern "C" hipError_t sr_launch_pick(const sr_dev_scene* sc, const float* segs, const sr_dev_frame* fr,
+                                     const float* ps, size_t ps_n, int32_t* out, size_t pitch, size_t frame_stride,
+                                     hipStream_t stream);
 
 namespace {
 
@@ -137,6 +150,21 @@ struct sr_ctx {
     int timing_cap = 0;
     int timing_n = 0;
     std::map<std::pair<int, int>, Table> tables;  // (max_steps, max_revolutions) -> table
+    // the retained frame (sr.h "Retained frames"): what the pixel state holds
+    // since the last launch, for sr_reshade and sr_pick_map. fr is the
+    // launch's own frame struct (a supersampled launch's: the sample frame's);
+    // the step table is re-ensured from its key. ss > 1: the resolve's
+    // arguments, in output pixels.
+    struct Retained {
+        bool valid = false;
+        sr_dev_frame fr;
+        int max_steps = 0, max_revolutions = 0;
+        int ss = 1;
+        int width = 0, height = 0, rows = 0, block_rows = 0;
+        const int* d_blocks = nullptr;
+    } kept;
+    // the scene of the last successful sr_set_scene (sr_scene_shading_only's left side)
+    sr_scene scene_src;
 };
 
 namespace {
@@ -639,6 +667,7 @@ bool wait_ctx(sr_ctx* ctx) {
 }
 
 void free_pixel_state(sr_ctx* ctx, hipStream_t s) {
+    ctx->kept.valid = false;  // the retained rays go with the planes
     release(ctx, ctx->d_ps, s);
     release(ctx, ctx->d_list, s);
     release(ctx, ctx->d_count, s);
@@ -829,6 +858,7 @@ int ensure_block_list(sr_ctx* ctx, const int* blocks, int n, hipStream_t s, cons
                     ++o;
                 }
             }
+            if (ctx->kept.fr.block_list == b.dev || ctx->kept.d_blocks == b.dev) ctx->kept.valid = false;
             release(ctx, b.dev, ctx->last_stream);
         });
     }
@@ -1098,6 +1128,7 @@ int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* pa
     fr.block_list = d_block_list;
     fr.wave_cost = d_wave_cost;
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    ctx->kept.valid = false;  // from here on the pixel state is this launch's
     rc = enter_stream(ctx, s);
     if (rc != SR_OK) return rc;
     const float4* tbl = nullptr;
@@ -1123,6 +1154,69 @@ int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* pa
                                       s);
     if (hip_ok(e)) e = hipEventRecord(ctx->order_ev, s);
     ctx->launched = true;
+    // the retained frame: whole launches of at least one row (a sparse launch
+    // holds only its tiles' rays, sr_wave_costs writes no pixels; the callers
+    // that launch more after this one, launch_ss and the rest, amend or drop it)
+    if (hip_ok(e) && nrows > 0 && !d_codes && !d_wave_cost) {
+        ctx->kept.fr = fr;
+        ctx->kept.max_steps = params->max_steps;
+        ctx->kept.max_revolutions = params->max_revolutions;
+        ctx->kept.ss = 1;
+        ctx->kept.d_blocks = nullptr;
+        ctx->kept.valid = true;
+    }
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
+}
+
+// The shading-only fields of a scene (sr.h "Retained frames") cleared: what is
+// left is what hit_opacity_uniform, the step loop, pack_object / pack_slot
+// and flat_miss_r2 can read.
+void clear_shading_fields(sr_scene& s) {
+    s.num_lights = 0;
+    std::memset(s.lights, 0, sizeof s.lights);
+    for (sr_material& m : s.materials) {
+        m.color[0] = m.color[1] = m.color[2] = 0.0f;
+        m.ambient = m.diffuse = m.specular = m.shininess = 0.0f;
+        m.normal_map_index = 0;
+    }
+}
+
+// sr_reshade and sr_reshade_debug: the retained launch's shade and resume
+// kernels again with the context's current scene, background and textures.
+int reshade(sr_ctx* c, uint8_t* out, size_t pitch, size_t frame_stride, float* dbg_rgba, int32_t* dbg_steps,
+            sr_stream stream) {
+    const sr_ctx::Retained& k = c->kept;
+    const int n_frames = k.fr.batch;
+    const bool ss = k.ss > 1;
+    const int width = ss ? k.width : k.fr.width, rows = ss ? k.rows : k.fr.nrows;
+    if (out && pitch < (size_t)width * 4) return SR_E_INVALID;
+    if (n_frames > 1 && (!out || frame_stride < pitch * (size_t)rows)) return SR_E_INVALID;
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    const float4* tbl = nullptr;
+    rc = ensure_table(c, k.max_steps, k.max_revolutions, s, &tbl);
+    if (rc != SR_OK) return rc;
+    sr_dev_frame fr = k.fr;
+    fr.bg_w = c->bg_w;  // sr_set_background keeps the frame: its current image
+    fr.bg_h = c->bg_h;
+    const size_t spitch = (size_t)k.width * 4 * (size_t)k.ss;
+    const size_t sstride = spitch * (size_t)k.rows * (size_t)k.ss;
+    if (ss) {
+        rc = ensure_sample_scratch(c, sstride * (size_t)n_frames, s);
+        if (rc != SR_OK) return rc;
+        fr.out_frame_stride = (int64_t)(n_frames > 1 ? sstride : 0);
+    } else {
+        fr.out_frame_stride = (int64_t)frame_stride;
+    }
+    hipError_t e = sr_launch_reshade(c->d_scene, tbl, c->d_segs, c->d_bg, c->d_arr, &fr, ss ? c->d_ss : out,
+                                     ss ? spitch : pitch, dbg_rgba, dbg_steps, c->d_ps, c->ps_n, c->d_list, c->d_count,
+                                     c->d_diag, s);
+    if (hip_ok(e) && ss)
+        e = sr_resolve_box_device(c->d_ss, spitch, sstride, k.width, k.rows, k.ss, k.d_blocks, k.block_rows, k.height,
+                                  out, pitch, frame_stride, n_frames, s);
+    if (hip_ok(e)) e = hipEventRecord(c->order_ev, s);
+    c->launched = true;
     return hip_ok(e) ? SR_OK : SR_E_HIP;
 }
 
@@ -1137,10 +1231,6 @@ extern "C" int sr_assemble_blocks_host(const uint8_t* stacked, size_t rank_strid
                                        size_t row_bytes, uint8_t* out, size_t out_frame_stride, int n_frames);
 
 // resolve.hip
-extern "C" hipError_t sr_resolve_box_device(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride,
-                                            int width, int rows, int ss, const int* dev_blocks, int block_rows,
-                                            int height, uint8_t* out, size_t pitch, size_t out_frame_stride,
-                                            int n_frames, hipStream_t stream);
 extern "C" void sr_resolve_box_host(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride, int width,
                                     int rows, int ss, uint8_t* out, size_t pitch, size_t out_frame_stride,
                                     int n_frames);
@@ -1311,6 +1401,7 @@ int sr_set_background(sr_ctx* c, const uint8_t* px, int w, int h, int ch) {
 int sr_set_texture_array(sr_ctx* c, const uint8_t* px, int w, int h, int layers, int ch) {
     if (!c || !px || w <= 0 || h <= 0 || layers <= 0 || (ch != 3 && ch != 4)) return SR_E_INVALID;
     if (!hip_ok(hipSetDevice(c->device)) || !wait_ctx(c)) return SR_E_HIP;
+    c->kept.valid = false;  // the rays' opacity classes read the array (hit_opacity_uniform)
     int rc = upload_rgba(c, px, w, h, layers, ch, &c->d_arr);
     if (rc == SR_OK) rc = make_opacity_map(c, px, w, h, layers, ch, &c->d_opq);
     if (rc != SR_OK) {
@@ -1489,11 +1580,17 @@ int sr_set_scene(sr_ctx* c, const sr_scene* s) {
     std::memcpy(d.planes, s->planes, sizeof d.planes);
     std::memcpy(d.texture_sizes, s->texture_sizes, sizeof d.texture_sizes);
     std::memcpy(d.max_texture_size, s->max_texture_size, sizeof d.max_texture_size);
+    // the retained frame outlives a change of shading-only fields alone
+    const bool keep = c->scene_set && sr_scene_shading_only(&c->scene_src, s) == 1;
     if (!hip_ok(hipSetDevice(c->device)) || !wait_ctx(c)) return SR_E_HIP;
+    if (!keep) c->kept.valid = false;
     if (!hip_ok(hipMemcpyAsync(c->d_scene, &d, sizeof d, hipMemcpyHostToDevice, c->upload)) ||
-        !hip_ok(hipStreamSynchronize(c->upload)))
+        !hip_ok(hipStreamSynchronize(c->upload))) {
+        c->kept.valid = false;
         return SR_E_HIP;
+    }
     c->h_scene = d;
+    c->scene_src = *s;
     c->xc_uf = c->xc_dphi = NAN;  // xlow_need, xperi_e again at the next launch
     c->scene_set = true;
     return SR_OK;
@@ -1502,6 +1599,7 @@ int sr_set_scene(sr_ctx* c, const sr_scene* s) {
 int sr_set_test_ray(sr_ctx* c, const sr_test_ray* t) {
     if (!c || !t) return SR_E_INVALID;
     if (t->num_curved_points < 0 || t->num_curved_points > SR_MAX_POINTS) return SR_E_CAPACITY;
+    c->kept.valid = false;  // the test ray is geometry of the retained rays
     sr_dev_scene d = c->h_scene;
     d.tr_visible = t->visible ? 1 : 0;
     d.tr_radius = t->radius;
@@ -1693,6 +1791,16 @@ static int launch_ss(sr_ctx* c, const sr_camera* cams, int n_frames, const sr_pa
                                          pitch, frame_stride, n_frames, s);
     // again at the end of the whole: a launch on another stream waits for the resolve too
     if (hip_ok(e)) e = hipEventRecord(c->order_ev, s);
+    if (hip_ok(e) && c->kept.valid) {  // the retained frame is the sample frame and this resolve
+        c->kept.ss = ss;
+        c->kept.width = width;
+        c->kept.height = height;
+        c->kept.rows = rows;
+        c->kept.block_rows = block_rows;
+        c->kept.d_blocks = d_blocks;
+    } else {
+        c->kept.valid = false;
+    }
     return hip_ok(e) ? SR_OK : SR_E_HIP;
 }
 
@@ -1716,7 +1824,10 @@ int sr_render_ss(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width,
     const int n = row_end - row_begin;
     if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss || n > (1 << 24) / ss)
         return SR_E_INVALID;
-    if (n == 0) return SR_OK;  // no rows: nothing is written
+    if (n == 0) {  // no rows: nothing is written
+        c->kept.valid = false;
+        return SR_OK;
+    }
     return launch_ss(c, cam, 1, p, width, height, n, row_begin, n, nullptr, ss, out, pitch, 0, stream);
 }
 
@@ -1774,6 +1885,7 @@ int sr_render_accumulate(sr_ctx* c, const sr_camera* cam, const sr_params* p, in
     if (width > INT32_MAX / 8 || accum_pitch < (size_t)width * 8 || (((uintptr_t)accum | accum_pitch) & 7) != 0)
         return SR_E_INVALID;
     const int n = row_end - row_begin;
+    c->kept.valid = false;  // the phases' frames are not a caller's output: nothing is retained
     if (n == 0) return SR_OK;  // no rows: nothing is written
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     rc = enter_stream(c, s);
@@ -1783,6 +1895,7 @@ int sr_render_accumulate(sr_ctx* c, const sr_camera* cam, const sr_params* p, in
     if (rc != SR_OK) return rc;
     rc = launch(c, cam, n_phases, p, width, height, n, row_begin, n, 0, c->d_ss, ipitch, istride, nullptr, nullptr,
                 stream, nullptr, nullptr, nullptr, ss, phases);
+    c->kept.valid = false;
     if (rc != SR_OK) return rc;
     hipError_t e = sr_accum_add_device(c->d_ss, ipitch, istride, n_phases, width, n, reset ? 1 : 0, accum, accum_pitch, s);
     // again at the end of the whole: a launch on another stream waits for the add too
@@ -1868,6 +1981,7 @@ int sr_render_adaptive(sr_ctx* c, const sr_camera* cam, const sr_params* p, int 
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (threshold >= 255) {  // no tile can be flagged: the plain frame, no sample work
         rc = launch(c, cam, 1, p, width, height, height, 0, height, 0, out, pitch, 0, nullptr, nullptr, stream);
+        c->kept.valid = false;  // no retained frame after an adaptive call, whatever it launched
         if (rc != SR_OK || !dev_tile_mask) return rc;
         hipError_t e = hipMemsetAsync(dev_tile_mask, 0, tiles, s);
         if (hip_ok(e)) e = hipEventRecord(c->order_ev, s);
@@ -1885,6 +1999,7 @@ int sr_render_adaptive(sr_ctx* c, const sr_camera* cam, const sr_params* p, int 
     if (rc != SR_OK) return rc;
     // P: the ordinary launch, which runs and learns the plain frame's order
     rc = launch(c, cam, 1, p, width, height, height, 0, height, 0, out, pitch, 0, nullptr, nullptr, stream);
+    c->kept.valid = false;  // the sparse sample launch below overwrites P's rays
     if (rc != SR_OK) return rc;
     hipError_t e = sr_edge_tiles_device(out, pitch, width, height, threshold, grow, c->d_amask, s);
     // the sample tiles in the order P's launch just learned (its shade kernel wrote it): costliest first
@@ -1910,6 +2025,50 @@ int sr_render_debug(sr_ctx* c, const sr_camera* cam, const sr_params* p, int wid
     int n = row_end - row_begin;
     return launch(c, cam, 1, p, width, height, n, row_begin, n > 0 ? n : 1, 0, out, (size_t)width * 4, 0, dbg_rgba,
                   dbg_steps, stream);
+}
+
+// ---- retained frames (sr.h): the pixel state of the context's last launch,
+// shaded again (sr_reshade) or read for its first surfaces (sr_pick_map)
+
+int sr_scene_shading_only(const sr_scene* a, const sr_scene* b) {
+    if (!a || !b) return 0;
+    sr_scene x = *a, y = *b;
+    clear_shading_fields(x);
+    clear_shading_fields(y);
+    return std::memcmp(&x, &y, sizeof x) == 0 ? 1 : 0;  // bytes: a NaN equals itself
+}
+
+int sr_can_reshade(sr_ctx* c) { return c && c->scene_set && c->kept.valid ? 1 : 0; }
+
+int sr_reshade(sr_ctx* c, uint8_t* out, size_t pitch, size_t frame_stride, sr_stream stream) {
+    if (!c) return SR_E_INVALID;
+    if (!sr_can_reshade(c)) return SR_E_NOT_READY;
+    if (!out) return SR_E_INVALID;
+    return reshade(c, out, pitch, frame_stride, nullptr, nullptr, stream);
+}
+
+int sr_reshade_debug(sr_ctx* c, float* dbg_rgba, uint8_t* out, int32_t* dbg_steps, sr_stream stream) {
+    if (!c) return SR_E_INVALID;
+    if (!sr_can_reshade(c)) return SR_E_NOT_READY;
+    if (c->kept.fr.batch != 1 || c->kept.ss > 1) return SR_E_INVALID;
+    if (!dbg_rgba && !out && !dbg_steps) return SR_E_INVALID;
+    return reshade(c, out, (size_t)c->kept.fr.width * 4, 0, dbg_rgba, dbg_steps, stream);
+}
+
+int sr_pick_map(sr_ctx* c, int32_t* ids, size_t pitch, size_t frame_stride, sr_stream stream) {
+    if (!c) return SR_E_INVALID;
+    if (!sr_can_reshade(c) || c->kept.ss > 1) return SR_E_NOT_READY;
+    const sr_dev_frame& fr = c->kept.fr;
+    if (!ids || ((uintptr_t)ids & 3) != 0 || (pitch & 3) != 0 || pitch < (size_t)fr.width * 4) return SR_E_INVALID;
+    if (fr.batch > 1 && ((frame_stride & 3) != 0 || frame_stride < pitch * (size_t)fr.nrows)) return SR_E_INVALID;
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    hipError_t e = sr_launch_pick(c->d_scene, c->d_segs, &fr, c->d_ps, c->ps_n, ids, pitch,
+                                  fr.batch > 1 ? frame_stride : 0, s);
+    if (hip_ok(e)) e = hipEventRecord(c->order_ev, s);
+    c->launched = true;
+    return hip_ok(e) ? SR_OK : SR_E_HIP;
 }
 
 int sr_abi_struct_sizes(size_t* out, int n) {
@@ -1971,6 +2130,20 @@ int sr_debug_pixel_state(sr_ctx* c, float* out, size_t max_floats, size_t* n_px)
     if (!hip_ok(hipMemcpyAsync(out, c->d_ps, k * sizeof(float), hipMemcpyDeviceToHost, c->upload)) ||
         !hip_ok(hipStreamSynchronize(c->upload)))
         return SR_E_HIP;
+    return SR_OK;
+}
+
+// Not in sr.h's public set: the retained launch's output shape for the
+// bindings: out[0 .. 3] = width, rows and frames of its output, and its ss
+// (1: plain). SR_E_NOT_READY without a retained frame.
+int sr_debug_retained_shape(sr_ctx* c, int* out4) {
+    if (!c || !out4) return SR_E_INVALID;
+    if (!sr_can_reshade(c)) return SR_E_NOT_READY;
+    const bool ss = c->kept.ss > 1;
+    out4[0] = ss ? c->kept.width : c->kept.fr.width;
+    out4[1] = ss ? c->kept.rows : c->kept.fr.nrows;
+    out4[2] = c->kept.fr.batch;
+    out4[3] = c->kept.ss;
     return SR_OK;
 }
 

@@ -365,6 +365,65 @@ class Renderer:
         )
         return f, b, s
 
+    # ---- retained frames (sr.h): relight and pick from the last launch's rays ----
+    def can_reshade(self) -> bool:
+        """sr_can_reshade: the context holds a retained frame reshade() would accept."""
+        return bool(self.lib.sr_can_reshade(self.ctx))
+
+    def _retained_shape(self, what: str):
+        """(width, rows, frames, ss) of the retained launch's output."""
+        buf = (C.c_int * 4)()
+        abi.check(self.lib.sr_debug_retained_shape(self.ctx, buf), what)
+        return tuple(int(v) for v in buf)
+
+    def reshade(self, out=None, stream=None):
+        """sr_reshade: the retained launch's frame(s) again from its rays, with
+        the current scene, background and textures -> a uint8 tensor shaped
+        like that launch's output ([rows, W, 4], or [B, rows, W, 4] for a batch
+        or a block list). Asynchronous."""
+        w, rows, frames, _ = self._retained_shape("sr_reshade")
+        if out is None:
+            shape = (rows, w, 4) if frames == 1 else (frames, rows, w, 4)
+            out = self.torch.empty(shape, dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and out.numel() >= frames * rows * w * 4
+        abi.check(self.lib.sr_reshade(self.ctx, C.c_void_p(out.data_ptr()), w * 4, rows * w * 4, self._stream(stream)),
+                  "sr_reshade")
+        return out
+
+    def reshade_debug(self, stream=None):
+        """sr_reshade_debug: (float RGBA FragColor, RGBA8, executed steps) of the
+        retained launch (one frame, not supersampled), as render_debug returns them."""
+        t = self.torch
+        w, rows, _, _ = self._retained_shape("sr_reshade_debug")
+        f = t.empty((rows, w, 4), dtype=t.float32, device=self.tdev)
+        b = t.empty((rows, w, 4), dtype=t.uint8, device=self.tdev)
+        s = t.empty((rows, w), dtype=t.int32, device=self.tdev)
+        abi.check(self.lib.sr_reshade_debug(self.ctx, C.c_void_p(f.data_ptr()), C.c_void_p(b.data_ptr()),
+                                            C.c_void_p(s.data_ptr()), self._stream(stream)), "sr_reshade_debug")
+        return f, b, s
+
+    def pick_map(self, out=None, stream=None):
+        """sr_pick_map: per pixel of the retained launch the index into
+        scene.objects[] of the first surface on its (bent) ray, or an
+        abi.PICK_* code -> int32 [rows, W] ([B, rows, W] for a batch or a
+        block list; rows the launch left unwritten are left unwritten). Asynchronous."""
+        w, rows, frames, ss = self._retained_shape("sr_pick_map")
+        if out is None:
+            shape = (rows, w) if frames == 1 else (frames, rows, w)
+            out = self.torch.full(shape, abi.PICK_NONE, dtype=self.torch.int32, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.int32 and out.numel() >= frames * rows * w
+        abi.check(self.lib.sr_pick_map(self.ctx, C.c_void_p(out.data_ptr()), w * 4, rows * w * 4, self._stream(stream)),
+                  "sr_pick_map")
+        return out
+
+    def pick(self, x: int, y: int, frame: int = 0) -> int:
+        """One entry of pick_map: output column x, output row y (row 0 = the
+        launch's first row, GL order) of frame `frame`. Waits for the map."""
+        m = self.pick_map()
+        if m.dim() == 3:
+            m = m[frame]
+        return int(m[int(y), int(x)].item())
+
     def close(self) -> None:
         if self.ctx:
             self.lib.sr_destroy(self.ctx)
