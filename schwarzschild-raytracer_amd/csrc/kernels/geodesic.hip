@@ -668,6 +668,9 @@ __device__ __forceinline__ float nmin(float m, float e) { return __builtin_eleme
 #ifndef SR_RETIRE_COAST  // lanes whose ray ends at a u_f crossing retire inside the coasting loop (integrate)
 #define SR_RETIRE_COAST 1
 #endif
+#ifndef SR_PARK_CERTAIN  // of those, lanes whose reseed is certain to end the ray are parked without it (certain_end)
+#define SR_PARK_CERTAIN 1
+#endif
 // The budget state's LDS rows (one column per thread) for an
 // instantiation with NB budget slots and NC budgeted cylinders: E[0..NB],
 // then pa[k], pb[k] (rows PA0 + 2k, + 1) and the slab budgets H[k] (SLAB0 +
@@ -2508,6 +2511,24 @@ __device__ __forceinline__ bool flat_misses(const sr_dev_scene* __restrict__ sc,
     return !sc->tr_visible && dot(ro, rd) >= 0.0f && dot(ro, ro) > sc->flat_miss_r2;
 }
 
+// A reseed that is certain to end the ray, told from the chord's two radii
+// alone (DESIGN.md §5 "A certain end"): u after step i - 1, up after step
+// i - 2 in the same orbital frame, r2 = fr.uf_radius2. The chord runs from
+// |A| = 1 / up out to |B| = 1 / u >= |A| (1 + 2^-10), so B . (B - A) > 0 and
+// sphere_lambda_r2's b = dot(rd, ro) is positive, and |B|^2 exceeds r2 by
+// 2^-9 |B|^2: its D is negative or sqrtf(D) < b, both roots are negative,
+// lam = -1 and it returns false, each by a margin a thousand times the
+// rounding of the chord (4e-6 relative in the end points). The bounds on u
+// keep every intermediate finite and normal. False for u <= 0, NaN or inf.
+#define SR_END_DELTA 0x1.ff8p-1f  // 1 - 2^-10
+#define SR_END_R2 0x1.ffp-1f      // 1 - 2^-9
+__device__ __forceinline__ bool certain_end(float u, float up, float r2) {
+    return u >= 0x1p-40f && u < 1.0f && up < 1.0e30f && u * u * r2 < SR_END_R2 && u <= up * SR_END_DELTA;
+}
+// a lane parked by certain_end, its reseed's ending half still to run
+// (integrate: `park`); no ST_ value
+#define SR_ST_PENDING 7
+
 // The step loop, frag:890-933, from step r.i (entry: r.u = u after step
 // r.i - 1, r.ro / r.rd = that step's chord end and direction).
 //
@@ -2602,15 +2623,19 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
     // ray (ST_BG / ST_FLAT: r.steps, r.rd and r.ro are final) or -1: the ray
     // goes on in its new orbital frame, its next chord forced. The one copy,
     // called at the top of the step loop and where the coasting loop retires
-    // lanes in place (SR_RETIRE_COAST).
-    auto reseed = [&](int i) -> int {
+    // lanes in place (SR_RETIRE_COAST). ENDING: the half that ends a ray, for
+    // a lane that certain_end() parked with its operands stashed: the same
+    // float operations on them, without the charge a continuing ray needs.
+    auto reseed_as = [&](int i, auto ending_tag) -> int {
+        constexpr bool ENDING = decltype(ending_tag)::value;
+        SR_PROBE(SR_RETIRE_STAT(7, 1));  // executions (divergent code)
         r.i = i;
         r.steps = sbase + i + 1;
         settle_prev(i);
         // the new orbital plane has its own coordinates: charge the
         // displacement from the old centre to the chord start r.ro
         // here, the new chord at the forced event (reseeded)
-        if (CULL)
+        if (CULL && !ENDING)
         {
             const float ocx = bs.cx(), ocy = bs.cy();
             bs.setT(__builtin_fmaf(len(r.ro - (r.nv * ocx + r.tv * ocy)), 1.0101f,
@@ -2621,7 +2646,9 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
             return flat_misses(sc, r.ro, r.rd) ? ST_BG : ST_FLAT;
         const f3 q = r.ro + r.rd * lam;  // sphere_intersect's point (computed past the exit)
         r.nv = nrm(q);
-        if (fabsf(dot(r.rd, r.nv)) >= 1.0f - SR_EPS) return flat_misses(sc, r.ro, r.rd) ? ST_BG : ST_FLAT;
+        // (ENDING: certain_end() holds, so the sphere was missed above; a lane
+        // that got here all the same could only end)
+        if (ENDING || fabsf(dot(r.rd, r.nv)) >= 1.0f - SR_EPS) return flat_misses(sc, r.ro, r.rd) ? ST_BG : ST_FLAT;
         r.tv = nrm(cross(cross(r.nv, r.rd), r.nv));
         r.u = 1.0f / len(q);
         r.du = -r.u * dot(r.rd, r.nv) / dot(r.rd, r.tv);
@@ -2630,6 +2657,7 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         force = true;  // the chord starts at the exact r.ro
         return -1;
     };
+    auto reseed = [&](int i) -> int { return reseed_as(i, std::false_type{}); };
     // the coasting loop left with its continuing lanes already reseeded for
     // step i: u_f is not compared again before the next top (wave-uniform)
     bool reseeded_in_loop = false;
@@ -2798,7 +2826,12 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         // `park` (-1: live), r.rd / r.ro are final, and it runs on at the RK4
         // fixed point (u, u') = (0, 0) with the bounds (-inf, +inf), which
         // fires no exit and makes no NaN (every product is with +-0). Parked
-        // lanes return when the wave next leaves the loop. A lane whose
+        // lanes return when the wave next leaves the loop. A wave's escaping
+        // lanes cross u_f at three or so different steps, and the reseed is
+        // divergent code run for the few lanes of each: a lane whose reseed
+        // is certain to end its ray (certain_end) is parked without it,
+        // status SR_ST_PENDING, and the chords and statuses of all such
+        // lanes are computed together where they return. A lane whose
         // reseed goes on (its line re-enters the u_f sphere) takes the wave
         // out, to where the step loop stands after its own reseed block.
         // Returns the parked lane's packed status (status | steps << 3) or -1.
@@ -2851,7 +2884,20 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
                         ++i;
                         bool goes_on = false;
                         if (park < 0 && r.u < fr.u_f) {  // the loop top's test, at the top of step i
-                            const int st = reseed(i);
+                            // a certain end: parked with the reseed's operands in
+                            // two rows of its budget column (dead from here on); its
+                            // chord and status wait for the wave's exit from the loop
+                            const bool sure = SR_PARK_CERTAIN && certain_end(r.u, up, fr.uf_radius2);
+                            SR_PROBE(SR_RETIRE_STAT(4, __popcll(__ballot(sure)));
+                                     SR_RETIRE_STAT(5, __popcll(__ballot(!sure))));
+                            int st = SR_ST_PENDING;
+                            if (sure) {
+                                bs.st(BS::L::BT, up);
+                                bs.st(BS::L::BM, r.u);
+                                r.steps = sbase + i + 1;
+                            } else {
+                                st = reseed(i);
+                            }
                             if (st >= 0) {
                                 park = st | (r.steps << 3);
                                 r.u = 0.0f;
@@ -2920,6 +2966,15 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         SR_PT(0);
         if (SR_RETIRE_COAST && RECORD) {
             if (park >= 0) {  // the divergent return of the lanes retired in the loop
+                if ((park & 7) == SR_ST_PENDING) {
+                    // one pass for every lane parked on certain_end(), each
+                    // at its own step: the ending half of its reseed, on the
+                    // operands the handler stashed
+                    SR_PROBE(SR_RETIRE_STAT(6, 1));
+                    up = bs.ld(BS::L::BT);
+                    r.u = bs.ld(BS::L::BM);
+                    return reseed_as((park >> 3) - sbase - 1, std::true_type{});
+                }
                 r.steps = park >> 3;
                 return park & 7;
             }

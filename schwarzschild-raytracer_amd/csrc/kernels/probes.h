@@ -45,12 +45,12 @@ __device__ const uint8_t* sr_lane_mask;
 // so the build keeps the production register allocation as far as possible).
 //   0 fast loop  1 reseeds  2 slow-path entry + approximate chord  3 budget events phase 1
 //   4 exact chord + intersect  5 hit classification + log  6 budget events phase 2  7 wave total
-#define SR_PROF_N 28  // 0-6 sections, 7 wave total | max steps << 48, 8-15 re-anchors of budget slots 0-7,
+#define SR_PROF_N 32  // 0-6 sections, 7 wave total | max steps << 48, 8-15 re-anchors of budget slots 0-7,
                       // 22 budget_init, 23 kernel start to integrate (launch code, pixel, ray set-up),
                       // 16 budget events, 17 events spending only slot 0, 18 lanes spending slot 0 (sum),
                       // 19 slow-path entries, 20 event phase 1 up to the spent ballots (the rest
                       // in 3), 21 slow-path tail + top of the step loop (2: exit to the event),
-                      // 24-27 the fast-loop exits that are no budget event (SR_RETIRE_STAT 0-3)
+                      // 24-31 the fast-loop exits that are no budget event (SR_RETIRE_STAT 0-7)
 __device__ unsigned long long sr_prof[SR_PROF_N * (1 << 17)];
 #define SR_PT(k)                                                      \
     do {                                                              \
@@ -106,6 +106,8 @@ __device__ unsigned long long sr_prof[SR_PROF_N * (1 << 17)];
 // the wave's accumulator 24 + k):
 //   0 slow-path entries without an event   1 exit steps retired by the coasting loop
 //   2 lanes parked there   3 of (1), those after which the wave left because a reseed went on
+//   4 of (2), lanes parked without their reseed (certain_end)   5 lanes there that failed certain_end
+//   6 passes that finish the lanes of (4)   7 executions of the reseed (each a divergent block)
 #if defined(SR_STATS_RETIRE)
 #define SR_RETIRE_STAT(k, v) SR_STAT(44 + (k), v)
 #elif defined(SR_PROF)
@@ -324,7 +326,7 @@ __device__ __forceinline__ void probe_event(const sr_dev_scene* __restrict__ sc,
                 if (sm == (1u << jc) && !__ballot(own && !(h > dd[k]))) SR_STAT(50 + k, 1);
             }
         }
-#elif defined(SR_STATS_RETIRE)  // counters 44..47 are integrate()'s own (SR_RETIRE_STAT)
+#elif defined(SR_STATS_RETIRE)  // counters 44..51 are integrate()'s own (SR_RETIRE_STAT)
 #else
         if (!__ballot(!(vb < 0.0f))) SR_STAT(44, 1);  // the black hole's u window alone
         SR_STAT(45, __popcll(__ballot(event && !(q0 < INFINITY))));  // lanes whose ball was empty

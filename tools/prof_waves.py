@@ -15,7 +15,7 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-NREC = 28  # SR_PROF_N
+NREC = 32  # SR_PROF_N
 SECTIONS = ["fast", "reseed", "slow_entry", "budget_phase1", "exact_chord", "hit_class", "budget_phase2"]
 
 
@@ -74,6 +74,10 @@ def main():
     out["retired_exit_steps_all_waves"] = int(t[ok, 25].sum())
     out["lanes_parked_all_waves"] = int(t[ok, 26].sum())
     out["retired_left_for_continuing_reseed_all_waves"] = int(t[ok, 27].sum())
+    out["lanes_parked_without_reseed_all_waves"] = int(t[ok, 28].sum())
+    out["lanes_failing_certain_end_all_waves"] = int(t[ok, 29].sum())
+    out["finish_passes_all_waves"] = int(t[ok, 30].sum())
+    out["reseed_executions_all_waves"] = int(t[ok, 31].sum())
     out["unaccounted_cycles_all_waves"] = int(total[ok].sum() - sums.sum() - t[ok, 20].sum() - t[ok, 21].sum()
                                               - t[ok, 22].sum() - t[ok, 23].sum())
     gx = (1920 + 15) // 16
