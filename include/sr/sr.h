@@ -687,6 +687,61 @@ int sr_set_split(sr_ctx* ctx, int max_tiles, int lanes_per_wave, int min_steps);
  * slower than split tiles alone. Off by default. */
 int sr_set_latency_mode(sr_ctx* ctx, int on);
 
+/* ---- Projections (not in the reference, whose camera is a pinhole with a
+ * field of view below 180 degrees). Context state like sr_set_split and
+ * sr_set_latency_mode, but unlike those it changes the pixels: it applies to
+ * every later launch of every kind (sr_render, sr_render_blocks,
+ * sr_render_blocks_batch, sr_render_block_list, sr_render_ss,
+ * sr_render_block_list_ss, sr_render_phase, sr_render_accumulate,
+ * sr_render_adaptive, sr_render_debug and sr_wave_costs, whose costs are
+ * those of the projected frame).
+ *
+ * Definition. All arithmetic is binary32 in the order written; sin and cos
+ * are the binary64 function of the float argument rounded to binary32
+ * (DESIGN.md §4). uv is the pixel's NDC as in every launch (under
+ * supersampling and phases the sample frame's), uvv = (uv.x, uv.y * res_y /
+ * res_x), a = fov / 360.0f * PI (the shader's own half angle, the argument of
+ * the tan behind its forward term), and the local direction L is
+ *   RECTILINEAR  (uvv.x, uvv.y, 1 / tan(a)): the reference's pinhole, frag:859-863
+ *   EQUIRECT     lon = uvv.x * a, lat = uvv.y * a, cl = cos(lat):
+ *                (cl * sin(lon), sin(lat), cl * cos(lon)); longitude and
+ *                latitude linear in the pixel, a 2:1 frame at fov 360 is the
+ *                whole sphere
+ *   FISHEYE      rho = sqrt(uvv.x * uvv.x + uvv.y * uvv.y), th = rho * a; the
+ *                pixel has no ray when !(th <= PI) (a NaN has none); else s =
+ *                sin(th) and L = rho > 0 ? (s * (uvv.x / rho), s * (uvv.y /
+ *                rho), cos(th)) : (0, 0, 1); the equidistant ("angular")
+ *                fisheye, a square frame at fov 180 is a dome master
+ * and rd = normalize(axes * L) for every projection. Everything after that is
+ * the reference's: the radial and flat tests, the split modes on uv, the
+ * noise mask on uvv and the crosshair on uv. A pixel with no ray ends exactly
+ * like one the noise mask blacked out (the test comes first, before the flat
+ * test): FragColor is the crosshair's initial value, it executes 0 steps and
+ * sr_pick_map reports SR_PICK_NONE.
+ *
+ * Setting a different projection drops the retained frame (the retained call
+ * issued again would walk other rays); setting the same value keeps it.
+ * sr_reshade, sr_reshade_debug and sr_pick_map work after a projected launch
+ * as after any other. Launch orders are learned per projection. The call
+ * touches host state only: no synchronisation, frames in flight keep the
+ * projection they were launched with. Under a projection other than
+ * RECTILINEAR the latency mode (sr_set_latency_mode) runs the default unroll;
+ * the pixels are the same either way. */
+#define SR_PROJECTION_RECTILINEAR 0   /* the reference's pinhole; the default */
+#define SR_PROJECTION_EQUIRECT    1   /* longitude / latitude, linear in the pixel */
+#define SR_PROJECTION_FISHEYE     2   /* equidistant ("angular") fisheye, dome masters */
+/* SR_E_INVALID for a null context or a projection outside 0 .. 2 (nothing changes) */
+int sr_set_projection(sr_ctx* ctx, int projection);
+/* the context's projection; SR_E_INVALID for a null context */
+int sr_get_projection(sr_ctx* ctx);
+/* Host only, no context: the local direction L by the rule above of pixel
+ * (px, py) of a plain uv_width x uv_height frame (for a supersampled launch:
+ * the sample frame's size and the sample's position), the same code the
+ * kernel runs. 1: out_local holds the pixel's L; 0: the pixel has no ray
+ * (out_local untouched); SR_E_INVALID for an unknown projection, a null
+ * output, sizes <= 0 or above INT32_MAX / 2, or a pixel off the frame. */
+int sr_projection_dir(int projection, float fov, int uv_width, int uv_height, int px, int py, float out_local[3]);
+
 /* Rows a sr_render_blocks call with these arguments writes. */
 int sr_blocks_row_count(int height, int block_rows, int block_first, int block_step);
 

@@ -220,7 +220,16 @@ SIGNATURES = {
     "sr_reshade": (_i, [_p, _p, C.c_size_t, C.c_size_t, _p]),
     "sr_reshade_debug": (_i, [_p, _p, _p, _p, _p]),
     "sr_pick_map": (_i, [_p, _p, C.c_size_t, C.c_size_t, _p]),
+    "sr_set_projection": (_i, [_p, _i]),
+    "sr_get_projection": (_i, [_p]),
+    "sr_projection_dir": (_i, [_i, C.c_float, _i, _i, _i, _i, C.POINTER(C.c_float)]),
 }
+# sr_set_projection's values (sr.h "Projections")
+PROJECTION_RECTILINEAR, PROJECTION_EQUIRECT, PROJECTION_FISHEYE = 0, 1, 2
+PROJECTIONS = {"rectilinear": PROJECTION_RECTILINEAR, "equirect": PROJECTION_EQUIRECT, "fisheye": PROJECTION_FISHEYE}
+# header functions a library built from an earlier revision lacks (the parent
+# build of an A/B timing, tools/bench_ab.sh): such a library still loads
+SINCE_PROJECTIONS = ("sr_set_projection", "sr_get_projection", "sr_projection_dir")
 # sr_pick_map's codes below the indices into scene.objects[]
 PICK_SKY, PICK_HOLE, PICK_TEST_RAY_FLAT, PICK_TEST_RAY_CURVED, PICK_NONE = -1, -2, -3, -4, -5
 MAX_SUPERSAMPLE = 4
@@ -259,8 +268,8 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         raise FileNotFoundError(f"{p} not built; run __graft_entry__.build() or make -C schwarzschild-raytracer_amd")
     lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **EXTRA_SIGNATURES}.items():
-        if name in EXTRA_SIGNATURES and not hasattr(lib, name):
-            continue  # debug tooling an older library (a bisection build) may lack
+        if (name in EXTRA_SIGNATURES or name in SINCE_PROJECTIONS) and not hasattr(lib, name):
+            continue  # debug tooling and newer calls an older library (a bisection build) may lack
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -279,6 +288,20 @@ def status_string(status: int) -> str:
 def check(status: int, what: str) -> None:
     if status != SR_OK:
         raise SRError(status, what)
+
+
+def projection_dir(projection: int, fov: float, uv_width: int, uv_height: int, px: int, py: int):
+    """sr_projection_dir: the local direction L (float32 [3]) of pixel (px, py)
+    of a uv_width x uv_height frame under `projection`, or None when the pixel
+    has no ray. Host only."""
+    import numpy as np
+
+    out = np.zeros(3, dtype=np.float32)
+    rc = load().sr_projection_dir(int(projection), float(fov), int(uv_width), int(uv_height), int(px), int(py),
+                                  out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc < 0:
+        raise SRError(rc, "sr_projection_dir")
+    return out if rc == 1 else None
 
 
 def write_png(path, frame, flip_rows: bool = True) -> None:

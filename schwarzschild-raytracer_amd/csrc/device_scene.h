@@ -310,6 +310,16 @@ typedef struct {
     // orbit's periapsis lies beyond every chord that could reach the object
     // (geodesic.hip SR_XPERI, sr_api.cpp xperi_e); -1: never excluded
     float xperi_e[SR_MAX_BUDGET];
+    // the context's projection (sr_set_projection, SR_PROJECTION_*): picks the
+    // integrate kernel's instantiation (geodesic.hip sr_launch_geodesic); no
+    // kernel reads it
+    int32_t projection;
+    // per frame of the batch, cam[f]'s fov / 360 * PI: the half angle behind
+    // ray_forward, what uv = 1 spans in the angular projections
+    // (sr/projection.hpp; the pinhole does not read it). Here at the struct's
+    // end and not in sr_dev_cam: a 64-byte camera stride changed the register
+    // count of kernels that index cam[] (DESIGN.md "Projections")
+    float cam_a[SR_MAX_BATCH];
 } sr_dev_frame;
 
 // the orbit energy below which a cylinder's orbital-plane exclusion applies

@@ -25,6 +25,7 @@ __device__ __forceinline__ float4 ldc(const sr_cfloat4* p) {
 }
 
 #include "../device_scene.h"
+#include "sr/projection.hpp"
 
 namespace {
 
@@ -67,6 +68,17 @@ __device__ __forceinline__ float t_cos(float x) { return (float)cos((double)x); 
 __device__ __attribute__((noinline)) float t_asin(float x) { return (float)asin((double)x); }
 __device__ __attribute__((noinline)) float t_atan2(float y, float x) { return (float)atan2((double)y, (double)x); }
 __device__ __attribute__((noinline)) float t_pow(float x, float y) { return (float)pow((double)x, (double)y); }
+// sin / cos of the angular projections (init_pixel, before the step loop):
+// out of line like the above, so the binary64 code is emitted once and its
+// registers are the callee's, not the projected integrate instantiations'
+__device__ __attribute__((noinline)) float t_sin_ol(float x) { return t_sin(x); }
+__device__ __attribute__((noinline)) float t_cos_ol(float x) { return t_cos(x); }
+struct ProjSin {
+    __device__ __forceinline__ float operator()(float x) const { return t_sin_ol(x); }
+};
+struct ProjCos {
+    __device__ __forceinline__ float operator()(float x) const { return t_cos_ol(x); }
+};
 
 __device__ __forceinline__ f3 ld3(const float* p) { return F3(p[0], p[1], p[2]); }
 __device__ __forceinline__ m3 ldm(const float* a) {
@@ -2396,16 +2408,29 @@ __device__ __forceinline__ f4 crosshair_frag(const sr_dev_frame& fr, const sr_de
 // (u, du) of the geodesic. Returns ST_FLAT, ST_DONE or -1 (integrate).
 // st: the frame's start record, which holds nrm(ro) and 1 / len(ro) (build_start:
 // the same expressions on the camera position, once per frame)
-__device__ __forceinline__ int init_pixel(const sr_dev_frame& fr, const sr_dev_cam& cam, const sr_dev_start& st,
-                                          const Pix& q, Ray& r) {
+// PROJ: the launch's projection (sr.h "Projections"), a compile-time value:
+// the rectilinear instantiations hold no trace of the others. The local
+// direction is sr::projection_local_dir's, the host's own statement; a pixel
+// without a ray (the fisheye beyond th = PI) ends as one the noise mask
+// blacked out, before the flat test.
+// a: the camera's half angle (sr_dev_frame.cam_a; unread by the pinhole).
+template <int PROJ = SR_PROJECTION_RECTILINEAR>
+__device__ __forceinline__ int init_pixel(const sr_dev_frame& fr, const sr_dev_cam& cam, float a,
+                                          const sr_dev_start& st, const Pix& q, Ray& r) {
     f2 uv = sample_uv(fr, cam, q);
     f2 uvv = F2(uv.x, uv.y * fr.res_y / fr.res_x);
     m3 axes = ldm(cam.axes);
     r.ro = ld3(cam.pos);
-    r.rd = nrm(mv(axes, F3(uvv.x, uvv.y, cam.ray_forward)));
-    r.nv = ld3(st.nv);
+    float L[3];
+    const bool has_ray = sr::projection_local_dir<PROJ>(uvv.x, uvv.y, a, cam.ray_forward, ProjSin(), ProjCos(), L);
     r.steps = 0;
     r.i = 0;
+    if (PROJ != SR_PROJECTION_RECTILINEAR && !has_ray) {
+        r.rd = F3(0.0f, 0.0f, 0.0f);
+        return ST_DONE;
+    }
+    r.rd = nrm(mv(axes, F3(L[0], L[1], L[2])));
+    r.nv = ld3(st.nv);
     SR_PROBE(probe_ray_init(r));
     const bool flat = fr.raytrace_type == SR_RAYTRACE_FLAT ||
                       (fr.raytrace_type == SR_RAYTRACE_HALF_WIDTH && uv.x > 2.0f * fr.curved_percentage + -1.0f) ||
@@ -3269,8 +3294,10 @@ __global__ __launch_bounds__(64) void sr_start_table_kernel(const sr_dev_scene* 
 // has six, and phase 1 of an event runs over every slot of the capacity).
 // NC: budgeted cylinders it handles (SR_NC_SMALL with SR_NB_SMALL).
 // TR: the test-ray instantiation (the test ray budgeted, clearance_tr)
+// PROJ: the projection (init_pixel); the angular ones have instantiations of
+// their own (sr_launch_projected), the rectilinear ones are untouched by them
 template <bool CULL, bool WCOST = false, int NB = SR_MAX_BUDGET, int FU = SR_FAST_UNROLL, int NC = SR_NC_KERNEL,
-          bool TR = false>
+          bool TR = false, int PROJ = SR_PROJECTION_RECTILINEAR>
 __global__ __launch_bounds__(SR_WG, sr_integrate_waves(NB, NC)) void sr_integrate_kernel(
     const sr_dev_scene* __restrict__ sc, const float4* __restrict__ tbl, const float* __restrict__ segs,
     const uint32_t* __restrict__ arr, const uint8_t* __restrict__ opq, sr_dev_frame fr, float* __restrict__ ps_base,
@@ -3313,7 +3340,8 @@ __global__ __launch_bounds__(SR_WG, sr_integrate_waves(NB, NC)) void sr_integrat
         const PS& ps = log.ps;
         Ray r;
         Hit hit;
-        int st = init_pixel(fr, fr.cam[frame], start[frame], q, r);
+        int st = init_pixel<PROJ>(fr, fr.cam[frame], PROJ != SR_PROJECTION_RECTILINEAR ? fr.cam_a[frame] : 0.0f,
+                                  start[frame], q, r);
         SR_PROBE(st = wp.lane_mask(q.px, q.py, fr.width, st, ST_DONE); wp.ray_start(r));
         if (st < 0) st = integrate<CULL, true, WCOST, NB, FU, NC, TR>(sc, segs, tbl, fr, tx, r, hit, log, start + frame);
         const size_t id = log.id();
@@ -3583,6 +3611,35 @@ __global__ __launch_bounds__(SR_WG) void sr_resume_kernel(const sr_dev_scene* __
     }
 }
 
+// The integrate launch of an angular projection (sr.h "Projections"): four
+// instantiations per projection, each the widest of its kind, so that every
+// scene, the overlay (tested per chord, TR = false, as in the wave-cost
+// launches), culling off, the sparse launch and split tiles are covered:
+//   wave costs              all slots, as sr_launch_geodesic's own
+//   culling off             the reference's loop
+//   the small scene         SR_NB_SMALL slots (the default scene's)
+//   everything else         all slots
+// The latency mode's unroll is not instantiated: such a launch runs the
+// default unroll, with the same pixels (sr.h).
+template <int PROJ>
+static void launch_projected(bool wcost, bool cull, bool small, dim3 grid, hipStream_t stream, const sr_dev_scene* sc,
+                             const float4* tbl, const float* segs, const uint32_t* arr, const uint8_t* opq,
+                             const sr_dev_frame& fr, float* ps, size_t ps_n, int* count, int* order, int* cost,
+                             sr_dev_start* start) {
+    if (wcost)
+        hipLaunchKernelGGL((sr_integrate_kernel<true, true, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ>), grid,
+                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost, start);
+    else if (!cull)
+        hipLaunchKernelGGL((sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1, false, PROJ>), grid, dim3(SR_WG), 0,
+                           stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost, start);
+    else if (small)
+        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, false, PROJ>), grid,
+                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost, start);
+    else
+        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ>), grid,
+                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost, start);
+}
+
 // order/cost (optional, one int per workgroup tile): the launch order and
 // the cost feedback of order_tiles. order without cost is a sparse launch
 // (sr_render_adaptive): one frame, `order` a caller-made list of whole-tile
@@ -3610,6 +3667,7 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
     if (split < 0 || (split && (fr->split_log2 < 0 || fr->split_log2 > 4 || (fr->split_log2 & 1))))
         return hipErrorInvalidValue;
     if (nblocks > (1u << 22)) return hipErrorInvalidValue;  // tile << 8 stays a positive int
+    if (fr->projection < SR_PROJECTION_RECTILINEAR || fr->projection > SR_PROJECTION_FISHEYE) return hipErrorInvalidValue;
     const unsigned slots = nblocks + ((64u >> (split ? fr->split_log2 : 6)) - 1u) * (unsigned)split;
     const bool cull = fr->cull != 0;
     // the small instantiation (6 slots, 1 cylinder: 17 LDS rows) when the
@@ -3625,7 +3683,14 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
     // the frames' start records, on every launch (the cameras, the scene and
     // the schedule are the launch's own; the integrate time includes it)
     hipLaunchKernelGGL(sr_start_table_kernel, dim3(B), dim3(1), 0, stream, sc, segs, *fr, start);
-    if (fr->wave_cost && general)
+    const dim3 igrid(slots * B * SR_WG_PER_TILE);
+    if (fr->projection == SR_PROJECTION_EQUIRECT)
+        launch_projected<SR_PROJECTION_EQUIRECT>(fr->wave_cost != nullptr, cull, small, igrid, stream, sc, tbl, segs, arr,
+                                                 opq, *fr, ps, ps_n, count, order, cost, start);
+    else if (fr->projection == SR_PROJECTION_FISHEYE)
+        launch_projected<SR_PROJECTION_FISHEYE>(fr->wave_cost != nullptr, cull, small, igrid, stream, sc, tbl, segs, arr,
+                                                opq, *fr, ps, ps_n, count, order, cost, start);
+    else if (fr->wave_cost && general)
         hipLaunchKernelGGL((sr_integrate_kernel<true, true, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>),
                            dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream,
                            sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "device_scene.h"
+#include "sr/projection.hpp"
 #include "sr/sr.h"
 
 // Round 6: budgeted cylinders take the lateral margin SR_CYL_QMARGIN Sc^2 / r
@@ -97,9 +98,11 @@ struct sr_ctx {
         std::vector<int> host;  // source of the stream-ordered upload
         uint64_t used = 0;
     };
-    // (gx, gy, split_tiles, split_log2, block list): a block list's tiles have
-    // their own costs; the list is its device copy, one per distinct content
-    std::map<std::tuple<int, int, int, int, const int*>, Order> orders;
+    // (gx, gy, split_tiles, split_log2, block list, projection): a block
+    // list's tiles have their own costs; the list is its device copy, one per
+    // distinct content. A projection's frames have their own costs too: a
+    // pinhole frame never runs in an order learned from a panorama
+    std::map<std::tuple<int, int, int, int, const int*, int>, Order> orders;
     // device copies of the block lists of sr_render_block_list, by content
     // (the key is the upload's source)
     struct BlockList {
@@ -114,6 +117,7 @@ struct sr_ctx {
     // split tiles (sr_set_split): 0 = off
     int split_tiles = 0, split_log2 = 4, split_min_steps = 1;
     int fast_unroll = SR_FAST_UNROLL_DEFAULT;  // sr_set_latency_mode: 2
+    int projection = SR_PROJECTION_RECTILINEAR;  // sr_set_projection
     const int* last_order = nullptr;  // the launch codes of the context's last frame (its next frame's order)
     size_t last_slots = 0;
     // the stream of the context's last launch: a context is used from one
@@ -788,7 +792,7 @@ void evict_orders(sr_ctx* ctx) {
 // tile, -1 for the split grid's slots no tile uses yet.
 int ensure_order(sr_ctx* ctx, int gx, int gy, const int* list, hipStream_t s, int** order, int** cost) {
     const int split = ctx->split_tiles;
-    const auto key = std::make_tuple(gx, gy, split, split ? ctx->split_log2 : 0, list);
+    const auto key = std::make_tuple(gx, gy, split, split ? ctx->split_log2 : 0, list, ctx->projection);
     auto it = ctx->orders.find(key);
     if (it != ctx->orders.end()) {
         it->second.used = ++ctx->tick;
@@ -1094,6 +1098,8 @@ int launch(sr_ctx* ctx, const sr_camera* cams, int n_frames, const sr_params* pa
     fr.num_budget = ctx->h_scene.num_budget;
     fr.num_budget_cyl = __builtin_popcount((unsigned)ctx->h_scene.budget_cyl_mask);
     fr.tr_visible = ctx->h_scene.tr_visible ? 1 : 0;
+    fr.projection = ctx->projection;
+    for (int f = 0; f < n_frames; f++) fr.cam_a[f] = sr::projection_half_angle((phases ? cams : &cams[f])->fov);
     fr.win_ok = fr.uf_radius <= 100.0f;
     {  // the low-energy exclusions (xlow_need, xperi_e), per (u_f, step angle)
         if (!(ctx->xc_uf == fr.u_f && ctx->xc_dphi == fr.max_dphi)) {
@@ -2098,6 +2104,54 @@ int sr_set_latency_mode(sr_ctx* c, int on) {
     if (!c) return SR_E_INVALID;
     c->fast_unroll = on ? 2 : SR_FAST_UNROLL_DEFAULT;
     return SR_OK;
+}
+
+// Host state alone: a launch copies it into its own frame struct, so frames
+// in flight keep theirs and nothing is waited for. The launch orders are
+// keyed by the projection (ensure_order).
+int sr_set_projection(sr_ctx* c, int projection) {
+    if (!c || projection < SR_PROJECTION_RECTILINEAR || projection > SR_PROJECTION_FISHEYE) return SR_E_INVALID;
+    if (projection != c->projection) c->kept.valid = false;  // the retained call issued again would walk other rays
+    c->projection = projection;
+    return SR_OK;
+}
+
+int sr_get_projection(sr_ctx* c) { return c ? c->projection : SR_E_INVALID; }
+
+namespace {
+struct HostSin {
+    float operator()(float x) const { return (float)std::sin((double)x); }
+};
+struct HostCos {
+    float operator()(float x) const { return (float)std::cos((double)x); }
+};
+}  // namespace
+
+int sr_projection_dir(int projection, float fov, int uv_width, int uv_height, int px, int py, float out_local[3]) {
+    if (!out_local || uv_width <= 0 || uv_height <= 0 || px < 0 || py < 0 || px >= uv_width || py >= uv_height)
+        return SR_E_INVALID;
+    if (uv_width > INT32_MAX / 2 || uv_height > INT32_MAX / 2) return SR_E_INVALID;
+    // sample_uv and init_pixel's uvv (geodesic.hip) for a plain frame of this size
+    const float uvx = (float)(2 * px + 1) / (float)uv_width - 1.0f;
+    const float uvy = (float)(2 * py + 1) / (float)uv_height - 1.0f;
+    const float vy = uvy * (float)uv_height / (float)uv_width;
+    const float a = sr::projection_half_angle(fov);
+    const float fwd = 1.0f / (float)std::tan((double)a);  // build_cam
+    bool ray;
+    switch (projection) {
+    case SR_PROJECTION_RECTILINEAR:
+        ray = sr::projection_local_dir<SR_PROJECTION_RECTILINEAR>(uvx, vy, a, fwd, HostSin(), HostCos(), out_local);
+        break;
+    case SR_PROJECTION_EQUIRECT:
+        ray = sr::projection_local_dir<SR_PROJECTION_EQUIRECT>(uvx, vy, a, fwd, HostSin(), HostCos(), out_local);
+        break;
+    case SR_PROJECTION_FISHEYE:
+        ray = sr::projection_local_dir<SR_PROJECTION_FISHEYE>(uvx, vy, a, fwd, HostSin(), HostCos(), out_local);
+        break;
+    default:
+        return SR_E_INVALID;
+    }
+    return ray ? 1 : 0;
 }
 
 // Not in sr.h's public set: the launch codes order_tiles wrote at the end

@@ -59,6 +59,22 @@ class Renderer:
         """sr_set_latency_mode: a 2-step fast loop for one frame at a time (pixels unchanged)."""
         abi.check(self.lib.sr_set_latency_mode(self.ctx, 1 if on else 0), "sr_set_latency_mode")
 
+    def set_projection(self, projection) -> None:
+        """sr_set_projection: abi.PROJECTION_* or its name ("rectilinear", "equirect",
+        "fisheye") for every later launch; a change drops the retained frame."""
+        if isinstance(projection, str):
+            if projection not in abi.PROJECTIONS:
+                raise ValueError(f"unknown projection {projection!r}; one of {sorted(abi.PROJECTIONS)}")
+            projection = abi.PROJECTIONS[projection]
+        abi.check(self.lib.sr_set_projection(self.ctx, int(projection)), "sr_set_projection")
+
+    def get_projection(self) -> int:
+        """sr_get_projection: the context's abi.PROJECTION_* value."""
+        rc = self.lib.sr_get_projection(self.ctx)
+        if rc < 0:
+            raise abi.SRError(rc, "sr_get_projection")
+        return int(rc)
+
     def set_timing(self, capacity: int) -> None:
         """Record per-kernel HIP events for the next `capacity` frames (0: off)."""
         abi.check(self.lib.sr_debug_set_timing(self.ctx, int(capacity)), "sr_debug_set_timing")

@@ -11,6 +11,9 @@ hyperbolic trajectory (src/main.cpp:404-410) in batched launches.
                                   (4 x 4 samples only in the 16x16 tiles with an edge above 32 levels)
   python tools/render.py --progressive 4 --out pass_%02d.png
                                   (progressive supersampling: the frame after each of the 16 passes)
+  python tools/render.py --projection equirect --fov 360 --width 2048 --height 1024 --out pano.png
+  python tools/render.py --projection fisheye --fov 180 --width 1080 --height 1080 --out dome.png
+                                  (sr_set_projection: a 360 degree panorama, a dome master)
 """
 import argparse
 import sys
@@ -44,6 +47,12 @@ def main():
                     help="progressive supersampling on an SS x SS grid (Renderer.progressive): one sample phase per "
                          "launch in sr_phase_order, the frame so far written after each pass (--out with %%d for the "
                          "pass number); the last one is --ssaa SS's frame")
+    ap.add_argument("--projection", choices=["rectilinear", "equirect", "fisheye"], default="rectilinear",
+                    help="the camera projection of every frame (sr_set_projection): the reference's pinhole, "
+                         "longitude / latitude, or the equidistant fisheye")
+    ap.add_argument("--fov", type=float, default=None,
+                    help="the camera's field of view in degrees (default: the app's); under equirect and fisheye "
+                         "the angle the frame's width spans, up to 360")
     args = ap.parse_args()
     if args.progressive is not None and (args.ssaa != 1 or args.adaptive is not None or args.flyby > 0):
         ap.error("--progressive takes the grid itself: no --ssaa, --adaptive or --flyby")
@@ -64,29 +73,37 @@ def main():
         r.set_background(sc.skybox(2048, 1024))
         arr, _, _ = sc.default_texture_array()
     r.set_texture_array(arr)
+    r.set_projection(args.projection)
     params = abi.default_params(max_steps=args.max_steps, percent_black=args.percent_black,
                                 raytrace_type=MODES[args.mode])
     params.crosshair = 1 if args.crosshair else 0
     W, H = args.width, args.height
+
+    def camera():
+        cam = abi.default_camera()
+        if args.fov is not None:
+            cam.fov = args.fov
+        return cam
+
     if args.progressive is not None:
-        for k, frame in r.progressive(abi.default_camera(), params, W, H, args.progressive):
+        for k, frame in r.progressive(camera(), params, W, H, args.progressive):
             torch.cuda.synchronize()
             path = args.out % k if "%" in args.out else f"{Path(args.out).stem}_{k:02d}.png"
             abi.write_png(path, frame.cpu().numpy())
             print(f"wrote {path} ({k} of {args.progressive ** 2} passes)")
     elif args.flyby <= 0:
         if args.adaptive is not None:
-            frame, tiles = r.render_adaptive(abi.default_camera(), params, W, H, args.ssaa, args.adaptive, args.grow)
+            frame, tiles = r.render_adaptive(camera(), params, W, H, args.ssaa, args.adaptive, args.grow)
             torch.cuda.synchronize()
             print(f"supersampled {int(tiles.sum())} of {tiles.numel()} tiles")
         else:
-            frame = r.render_ss(abi.default_camera(), params, W, H, args.ssaa)
+            frame = r.render_ss(camera(), params, W, H, args.ssaa)
         torch.cuda.synchronize()
         abi.write_png(args.out, frame.cpu().numpy())
         print(f"wrote {args.out}")
     else:
         n = args.flyby
-        cams = [abi.camera_flyby((f + 0.5) / n, 30.0, 10.0) for f in range(n)]
+        cams = [abi.camera_flyby((f + 0.5) / n, 30.0, 10.0, cam=camera()) for f in range(n)]
         # up to 32 frames per launch, fewer while the sample scratch of a batch
         # (4 ssaa^2 W H bytes per frame) would pass 2 GiB
         per = max(1, min(32, (2 << 30) // (4 * args.ssaa ** 2 * W * H)))
