@@ -4,7 +4,9 @@ assets/shaders/black_hole.frag).
 
 Layout:
   csrc/kernels/geodesic.hip  the gfx950 kernel (one wave64 lane per ray)
-  csrc/sr_api.cpp            the C-ABI of include/sr/sr.h
+  csrc/sr_api.cpp            the C-ABI of include/sr/sr.h: context, uploads, dispatch
+  csrc/host/precompute.cpp   the host arithmetic behind the culling margins (no HIP)
+  csrc/kernels/launchers.h   the kernel files' host entries, declared once
   csrc/host/scene.cpp        the reference-shaped C++ scene model (include/sr/scene.hpp)
   abi.py                     ctypes mirror of sr.h
   renderer.py                Renderer: device handle (torch for memory/streams)

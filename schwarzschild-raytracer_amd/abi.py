@@ -243,6 +243,13 @@ EXTRA_SIGNATURES = {
     "sr_debug_last_order": (_i, [_p, C.POINTER(_i), _i, C.POINTER(_i)]),
     "sr_debug_pixel_state": (_i, [_p, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_size_t)]),
     "sr_debug_retained_shape": (_i, [_p, C.POINTER(_i)]),
+    # the host precomputation (csrc/host/precompute.cpp) without a device or a context
+    "sr_debug_precompute_sizes": (_i, [C.POINTER(C.c_size_t), _i]),
+    "sr_debug_pack_scene": (_i, [C.POINTER(Scene), C.POINTER(TestRay), _p, _p]),
+    "sr_debug_frame": (_i, [C.POINTER(Scene), C.POINTER(TestRay), C.POINTER(Camera), C.POINTER(Params), _i, _i, _i,
+                            _i, _p]),
+    "sr_debug_step_table": (_i, [_i, _i, _p, C.c_size_t]),
+    "sr_debug_opacity_bits": (_i, [_p, _i, _i, _i, _i, _p, C.c_size_t]),
 }
 
 _lib = None
@@ -413,6 +420,64 @@ def scene_shading_only(a: Scene, b: Scene) -> bool:
     """sr_scene_shading_only: b differs from a in lights and the materials'
     rgb, Phong terms and normal maps at most (a retained frame outlives it)."""
     return bool(load().sr_scene_shading_only(C.byref(a), C.byref(b)))
+
+
+def _precompute_sizes():
+    out = (C.c_size_t * 3)()
+    check(load().sr_debug_precompute_sizes(out, 3), "sr_debug_precompute_sizes")
+    return tuple(int(v) for v in out)
+
+
+def debug_pack_scene(scene: Scene | None, test_ray: TestRay | None = None):
+    """sr_debug_pack_scene: (status, scene image bytes, segment buffer bytes)
+    that sr_set_scene(scene) and sr_set_test_ray(test_ray) would upload on a
+    fresh context (None: no scene / the default test ray). Host only; the
+    buffers are None unless the status is SR_OK."""
+    import numpy as np
+
+    n_scene, n_segs, _ = _precompute_sizes()
+    img, segs = np.zeros(n_scene, dtype=np.uint8), np.zeros(n_segs, dtype=np.uint8)
+    rc = load().sr_debug_pack_scene(C.byref(scene) if scene is not None else None,
+                                    C.byref(test_ray) if test_ray is not None else None, img.ctypes.data,
+                                    segs.ctypes.data)
+    return (rc, img, segs) if rc == SR_OK else (rc, None, None)
+
+
+def debug_frame(scene: Scene | None, test_ray: TestRay | None, cam: Camera, params: Params, width: int, height: int,
+                cull: bool = True, projection: int = PROJECTION_RECTILINEAR):
+    """sr_debug_frame: (status, frame struct bytes) of a whole-frame sr_render
+    on that fresh context. Host only; None unless the status is SR_OK."""
+    import numpy as np
+
+    out = np.zeros(_precompute_sizes()[2], dtype=np.uint8)
+    rc = load().sr_debug_frame(C.byref(scene) if scene is not None else None,
+                               C.byref(test_ray) if test_ray is not None else None, C.byref(cam), C.byref(params),
+                               int(width), int(height), 1 if cull else 0, int(projection), out.ctypes.data)
+    return (rc, out) if rc == SR_OK else (rc, None)
+
+
+def debug_step_table(max_steps: int, max_revolutions: int):
+    """sr_debug_step_table: float32 [max_steps + 4, 4] rows {step, step / 6,
+    cos phi, sin phi} of the schedule, the last four rows zero padding."""
+    import numpy as np
+
+    out = np.empty((int(max_steps) + 4, 4), dtype=np.float32)
+    check(load().sr_debug_step_table(int(max_steps), int(max_revolutions), out.ctypes.data, out.size),
+          "sr_debug_step_table")
+    return out
+
+
+def debug_opacity_bits(arr):
+    """sr_debug_opacity_bits: the opacity bitmap of a [layers, h, w, 3 or 4]
+    uint8 texture array, uint8 [layers, h, ceil(w / 8)]."""
+    import numpy as np
+
+    a = np.ascontiguousarray(arr, dtype=np.uint8)
+    layers, h, w, ch = a.shape
+    out = np.empty((layers, h, (w + 7) // 8), dtype=np.uint8)
+    check(load().sr_debug_opacity_bits(a.ctypes.data, w, h, layers, ch, out.ctypes.data, out.size),
+          "sr_debug_opacity_bits")
+    return out
 
 
 def check_layout() -> dict:

@@ -1,6 +1,6 @@
 // device_scene.h — the launch-invariant scene image the kernel reads with
 // wave-uniform (scalar) loads. Built once per sr_set_scene / sr_set_test_ray
-// by the host packer (sr_api.cpp) from the GLSL-shaped sr_scene; every derived
+// by the host packer (host/precompute.cpp) from the GLSL-shaped sr_scene; every derived
 // value (box faces, test-ray frames, bounding spheres) is computed on the host
 // with the same float operations the shader performs per call, so the kernel's
 // results are bit-identical to evaluating them per step.
@@ -146,7 +146,7 @@ typedef struct {
 // where the next kernel reads them.
 #define SR_PS_HITS 4
 #define SR_PS_FIELDS (4 + 8 * SR_PS_HITS + 16)
-// Texture-array opacity bitmap radius (texels), see sr_api.cpp make_opacity_map
+// Texture-array opacity bitmap radius (texels), see precompute.cpp opacity_bits
 #define SR_OPQ_RADIUS 2
 
 // One test-ray cylinder: pos[3] axes[9] height radius, then 1 when its frame
@@ -158,7 +158,7 @@ typedef struct {
 // cone axis[3], cos alpha, sin alpha, max |pos|_1, always (1: no culling),
 // lateral-margin scale}: every segment's accepted points lie within R of the
 // centre and within the scale x lat_margin of its (frame's) lateral surface
-// (sr_api.cpp frame_norms: 1 + 1e-6 for an orthonormal frame); every segment
+// (precompute.cpp frame_norms: 1 + 1e-6 for an orthonormal frame); every segment
 // axis within alpha of the cone axis (unused since round 6).
 #define SR_TR_BLOCK 8
 #define SR_TR_GROUP 8
@@ -303,12 +303,12 @@ typedef struct {
     float bh_u2, bh_u3;
     // per budget slot j - 1: the orbital-plane distance of its bounding centre
     // beyond which no chord of a low-energy orbit (u < 0.6, u'^2 + u^2 (1 -
-    // u) <= SR_XCYL_EMAX) can reach it (geodesic.hip SR_XCYL, sr_api.cpp
+    // u) <= SR_XCYL_EMAX) can reach it (geodesic.hip SR_XCYL, precompute.cpp
     // xlow_need); +inf: never excluded
     float xlow_need[SR_MAX_BUDGET];
     // per budget slot j - 1: the orbit energy at or below which a low-energy
     // orbit's periapsis lies beyond every chord that could reach the object
-    // (geodesic.hip SR_XPERI, sr_api.cpp xperi_e); -1: never excluded
+    // (geodesic.hip SR_XPERI, precompute.cpp xperi_e); -1: never excluded
     float xperi_e[SR_MAX_BUDGET];
     // the context's projection (sr_set_projection, SR_PROJECTION_*): picks the
     // integrate kernel's instantiation (geodesic.hip sr_launch_geodesic); no
@@ -331,14 +331,14 @@ typedef struct {
 // SR_FAST_UNROLL)
 #define SR_FAST_UNROLL_DEFAULT 4
 // the largest step angle (max_angle / max_steps, here max_dphi) at which the
-// low-energy exclusions apply (sr_api.cpp clear_radius): their premises (E
+// low-energy exclusions apply (precompute.cpp clear_radius): their premises (E
 // conserved within 2 %, one step moving u by at most kappa, u never past the
 // periapsis root) are checked on the kernel's own binary32 RK4 up to it by
 // tests/test_low_energy_bounds.py (the app's MAX_STEPS 100 at up to three
 // revolutions: 0.1885); coarser schedules exclude nothing
 #define SR_XLOW_DPHI_MAX 0.2f
 
-// the inner black-hole window's margins (sr_api.cpp build_frame, geodesic.hip)
+// the inner black-hole window's margins (precompute.cpp derive_frame, geodesic.hip)
 #define SR_BH_G2 1.5e-3
 #define SR_BH_G3 6.0e-5
 #define SR_BH_S_DPHI 0.0132f

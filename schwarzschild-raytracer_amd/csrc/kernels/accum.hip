@@ -20,6 +20,8 @@
 
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr int kThreads = 256;

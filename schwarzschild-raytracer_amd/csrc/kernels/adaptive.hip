@@ -32,6 +32,8 @@
 
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr int kThreads = 256;

@@ -8,6 +8,8 @@
 
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 __global__ __launch_bounds__(256) void sr_assemble_kernel(const uint8_t* __restrict__ stacked, size_t rank_stride,

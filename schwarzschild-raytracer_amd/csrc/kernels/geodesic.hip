@@ -25,6 +25,7 @@ __device__ __forceinline__ float4 ldc(const sr_cfloat4* p) {
 }
 
 #include "../device_scene.h"
+#include "launchers.h"
 #include "sr/projection.hpp"
 
 namespace {
@@ -103,7 +104,7 @@ struct Hit {
 struct Tex {
     const uint32_t* __restrict__ bg;
     const uint32_t* __restrict__ arr;
-    const uint8_t* __restrict__ opq;  // texture-array opacity bitmap (sr_api.cpp make_opacity_map)
+    const uint8_t* __restrict__ opq;  // texture-array opacity bitmap (precompute.cpp opacity_bits)
 };
 
 #include "probes.h"
@@ -364,7 +365,7 @@ __device__ __forceinline__ void test_object(Hit& best, const sr_dev_obj& ob, int
 // The margin factor of a slot's distance tests: a planar primitive's
 // per-chord factor (SR_MU_PLANAR: it accepts a chord point within a few eps
 // S of its plane and bounds), the quadratic one for spheres and cylinders
-// (sr_api.cpp set_bound; the slab and in-plane margins sl.mp use the same).
+// (precompute.cpp set_bound; the slab and in-plane margins sl.mp use the same).
 __device__ __forceinline__ float slot_mu(const sr_dev_slot& sl) {
     return sl.type == SR_OBJECT_CYLINDER ? SR_MU_QUADRATIC : sl.mu;
 }
@@ -571,7 +572,7 @@ __device__ __forceinline__ float plane_window_dir(f3 wn, float k2r, float kap, f
 __device__ __forceinline__ bool outward_slot(const sr_dev_slot& sl, bool cyl_par, float a, float dip) {
     if (SR_OUT_CYL_CM) cyl_par = false;
     if (sl.type == SR_OBJECT_PLANE || (sl.type == SR_OBJECT_CYLINDER && (cyl_par || !(sl.x1 > 0.0f)))) return false;
-    if (SR_OUT_FAR)  // the object's own farthest point (sr_api.cpp far_reach), not its bounding sphere's
+    if (SR_OUT_FAR)  // the object's own farthest point (precompute.cpp far_reach), not its bounding sphere's
         return outward_clear(sl.rf, 0.0f, slot_mu(sl), sl.type == SR_OBJECT_CYLINDER ? sl.qk : 0.0f, sl.pl1, a, dip);
     return outward_clear(sl.cn, sl.br, sl.mu, sl.type == SR_OBJECT_CYLINDER ? sl.qk : 0.0f, sl.pl1, a, dip);
 }
@@ -654,7 +655,7 @@ __device__ __forceinline__ float nmin(float m, float e) { return __builtin_eleme
 // Budgeted cylinders whose nearly parallel chords the kernel handles apart
 // (chord_parallel, slab budgets, the cylinder-plane fast loops) in the
 // general and large instantiations and the resume kernel: none since round 6
-// (sr_api.cpp SR_CYL_DIRFREE: the lateral margin holds for every direction);
+// (precompute.cpp SR_CYL_DIRFREE: the lateral margin holds for every direction);
 // SR_MAX_CYLINDERS for a host built with SR_CYL_DIRFREE=0
 #ifndef SR_NC_KERNEL
 #define SR_NC_KERNEL 0
@@ -879,7 +880,7 @@ __device__ __forceinline__ uint32_t xplane_bit(const sr_dev_slot& sl, int j, f3 
     return plane_off_bit(ld3(sl.bc), j, n, nn, xplane_need(sl, xs));
 }
 // A bounded slot off a low-energy orbit's plane (SR_XCYL): need =
-// sr_dev_frame.xlow_need[j - 1] (sr_api.cpp xlow_need has the bound: the
+// sr_dev_frame.xlow_need[j - 1] (precompute.cpp xlow_need has the bound: the
 // chords that could come near the object by distance from the origin stay
 // short, so its margin mu S, and a cylinder's quadratic one, are small; the
 // orbital-plane exclusion's S_max gave a cylinder 31 units). A cylinder's
@@ -899,7 +900,7 @@ __device__ __forceinline__ float orbit_e(float u, float du) {
 }
 // Periapsis exclusion (SR_XPERI): a low-energy orbit never comes closer to
 // the origin than its periapsis, and an object whose every reachable chord
-// (sr_api.cpp clear_radius) lies inside that sphere is excluded for the
+// (precompute.cpp clear_radius) lies inside that sphere is excluded for the
 // orbit, like an orbital-plane exclusion (bits 8 + j, budget_frame). The
 // accretion disk, within r = 5 of the hole, is the default scene's case.
 #ifndef SR_XPERI
@@ -1620,7 +1621,7 @@ __device__ __forceinline__ void test_ray_hits(const sr_dev_scene* __restrict__ s
 // S and the lateral margin lat_margin (round 6: for every chord direction;
 // round 5 divided the quadratic's margin by |d_perp|^2 and tested every
 // segment of a block whose cone of axes held a chord's direction); decided
-// for a whole block or group of segments at once (sr_api.cpp
+// for a whole block or group of segments at once (precompute.cpp
 // test_ray_bounds: every segment's sphere lies within R of the bound's
 // centre). The survivors are the exhaustive loop's tests with the same keys,
 // so the winner is the same.
@@ -1706,7 +1707,7 @@ __device__ __forceinline__ float tr_clear_bound(const float* __restrict__ B, f3 
     return B[10] != 0.0f ? -INFINITY : d0 - m;
 }
 // One segment's capsule (its axis segment [pos, pos + h c1], radius r):
-// -inf unless its frame is orthonormal (q[14], sr_api.cpp); the frame's
+// -inf unless its frame is orthonormal (q[14], precompute.cpp); the frame's
 // 1e-5 tolerance moves lateral distances and the axis by at most 1e-5 of
 // them, inside the 3e-5 allowance
 __device__ __forceinline__ float tr_clear_segment(const float* __restrict__ q, f3 A, float l1A, float r) {
@@ -2305,7 +2306,7 @@ static_assert(PS_PLANES + 16 == SR_PS_FIELDS, "pixel-state layout");
 // key = slot * 8 + face in [-24, 167]: slots -3 .. SR_MAX_OBJECTS - 1
 #define PS_KEY_BIAS 24
 static_assert((SR_MAX_OBJECTS - 1) * 8 + 7 + PS_KEY_BIAS < 256, "hit key fits 8 bits");
-// steps <= SR_MAX_STEPS (sr_api.cpp build_frame): 24 bits
+// steps <= SR_MAX_STEPS (precompute.cpp check_frame_args): 24 bits
 static_assert(SR_MAX_STEPS < (1 << 24), "step count fits the packed word");
 __device__ __forceinline__ int ps_word(int st, int nh, int steps) {
     return (int)((uint32_t)st | ((uint32_t)nh << 3) | ((uint32_t)steps << 8));
@@ -3220,7 +3221,7 @@ __device__ __forceinline__ void write_pixel(const sr_dev_frame& fr, uint8_t* __r
 // budgeted cylinders of the small instantiation: its cylinder loops (phase 1,
 // chord_parallel in the cylinder-plane fast loop) run over one, and its LDS
 // layout holds 17 rows instead of 25 (no VGPR spills left in it)
-#ifndef SR_NC_SMALL  // round 6: 0 (no budgeted cylinder needs the direction tests, sr_api.cpp SR_CYL_DIRFREE)
+#ifndef SR_NC_SMALL  // round 6: 0 (no budgeted cylinder needs the direction tests, precompute.cpp SR_CYL_DIRFREE)
 #define SR_NC_SMALL 0
 #endif
 #ifndef SR_GENERAL_WAVES_PER_EU
@@ -3626,19 +3627,29 @@ static void launch_projected(bool wcost, bool cull, bool small, dim3 grid, hipSt
                              const float4* tbl, const float* segs, const uint32_t* arr, const uint8_t* opq,
                              const sr_dev_frame& fr, float* ps, size_t ps_n, int* count, int* order, int* cost,
                              sr_dev_start* start) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost,
+                           start);
+    };
     if (wcost)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, true, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ>), grid,
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, true, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ>);
     else if (!cull)
-        hipLaunchKernelGGL((sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1, false, PROJ>), grid, dim3(SR_WG), 0,
-                           stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1, false, PROJ>);
     else if (small)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, false, PROJ>), grid,
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, false, PROJ>);
     else
-        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ>), grid,
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ>);
 }
+
+#ifndef SR_RESUME_TILES  // the resume kernel's grid-stride grid, in 256-thread tiles
+#define SR_RESUME_TILES 1024u
+#endif
+// (defined below sr_launch_geodesic: the resume kernels are instantiated after
+// the integrate and shade kernels, as the code object lists them)
+static void launch_resume(bool tr, bool cull, unsigned tiles, hipStream_t stream, const sr_dev_scene* sc,
+                          const float4* tbl, const float* segs, const uint32_t* bg, const uint32_t* arr,
+                          const sr_dev_frame& fr, float* ps, size_t ps_n, uint8_t* out, size_t pitch, float* dbg_rgba,
+                          int32_t* dbg_steps, int* list, int* count);
 
 // order/cost (optional, one int per workgroup tile): the launch order and
 // the cost feedback of order_tiles. order without cost is a sparse launch
@@ -3684,6 +3695,10 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
     // the schedule are the launch's own; the integrate time includes it)
     hipLaunchKernelGGL(sr_start_table_kernel, dim3(B), dim3(1), 0, stream, sc, segs, *fr, start);
     const dim3 igrid(slots * B * SR_WG_PER_TILE);
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, igrid, dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost,
+                           start);
+    };
     if (fr->projection == SR_PROJECTION_EQUIRECT)
         launch_projected<SR_PROJECTION_EQUIRECT>(fr->wave_cost != nullptr, cull, small, igrid, stream, sc, tbl, segs, arr,
                                                  opq, *fr, ps, ps_n, count, order, cost, start);
@@ -3691,41 +3706,25 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
         launch_projected<SR_PROJECTION_FISHEYE>(fr->wave_cost != nullptr, cull, small, igrid, stream, sc, tbl, segs, arr,
                                                 opq, *fr, ps, ps_n, count, order, cost, start);
     else if (fr->wave_cost && general)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, true, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>),
-                           dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream,
-                           sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, true, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>);
     else if (fr->wave_cost)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, true>), dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream,
-                           sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, true>);
     else if (small && tr)  // the test-ray instantiations (the overlay visible)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, true>),
-                           dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps,
-                           ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, true>);
     else if (cull && general && tr)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL, true>),
-                           dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps,
-                           ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, false, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL, true>);
     else if (cull && tr)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, true>),
-                           dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps,
-                           ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, true>);
     else if (small && fr->fast_unroll == 2)  // latency mode (sr_set_latency_mode)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_SMALL, 2, SR_NC_SMALL>), dim3(slots * B * SR_WG_PER_TILE),
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, false, SR_NB_SMALL, 2, SR_NC_SMALL>);
     else if (small)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL>),
-                           dim3(slots * B * SR_WG_PER_TILE),
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL>);
     else if (cull && general)
-        hipLaunchKernelGGL((sr_integrate_kernel<true, false, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>),
-                           dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc,
-                           tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true, false, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>);
     else if (cull)
-        hipLaunchKernelGGL(sr_integrate_kernel<true>, dim3(slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc,
-                           tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<true>);
     else  // the reference's loop (no budgets: the smallest LDS layout)
-        hipLaunchKernelGGL((sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1>), dim3(slots * B * SR_WG_PER_TILE),
-                           dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost, start);
+        go(sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1>);
     if (ev4) (void)hipEventRecord(ev4[1], stream);
     OrderArgs oa{cost, sparse ? nullptr : order, (int)nblocks, fr->max_steps, split, split ? fr->split_log2 : 6, fr->split_min_steps};
     if (sparse)
@@ -3736,21 +3735,29 @@ extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* t
                            segs, bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa,
                            (const int*)nullptr);
     if (ev4) (void)hipEventRecord(ev4[2], stream);
-#ifndef SR_RESUME_TILES  // the resume kernel's grid-stride grid, in 256-thread tiles
-#define SR_RESUME_TILES 1024u
-#endif
-    unsigned nb = (nblocks * B < SR_RESUME_TILES ? nblocks * B : SR_RESUME_TILES) * SR_WG_PER_TILE;
-    if (tr)
-        hipLaunchKernelGGL((sr_resume_kernel<true, true>), dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr,
-                           ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count);
-    else if (cull)
-        hipLaunchKernelGGL(sr_resume_kernel<true>, dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n,
-                           out, pitch, dbg_rgba, dbg_steps, list, count);
-    else
-        hipLaunchKernelGGL(sr_resume_kernel<false>, dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n,
-                           out, pitch, dbg_rgba, dbg_steps, list, count);
+    launch_resume(tr, cull, nblocks * B, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list,
+                  count);
     if (ev4) (void)hipEventRecord(ev4[3], stream);
     return hipGetLastError();
+}
+
+// The resume kernel of a launch's kind (the test ray budgeted, culling on,
+// the reference's loop) over `tiles` 256-pixel tiles of pixel state.
+static void launch_resume(bool tr, bool cull, unsigned tiles, hipStream_t stream, const sr_dev_scene* sc,
+                          const float4* tbl, const float* segs, const uint32_t* bg, const uint32_t* arr,
+                          const sr_dev_frame& fr, float* ps, size_t ps_n, uint8_t* out, size_t pitch, float* dbg_rgba,
+                          int32_t* dbg_steps, int* list, int* count) {
+    const dim3 grid((tiles < SR_RESUME_TILES ? tiles : SR_RESUME_TILES) * SR_WG_PER_TILE);
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, fr, ps, ps_n, out, pitch, dbg_rgba,
+                           dbg_steps, list, count);
+    };
+    if (tr)
+        go(sr_resume_kernel<true, true>);
+    else if (cull)
+        go(sr_resume_kernel<true>);
+    else
+        go(sr_resume_kernel<false>);
 }
 
 // ---- retained frames (sr.h): the pixel state a launch left, shaded again or
@@ -3780,16 +3787,8 @@ extern "C" hipError_t sr_launch_reshade(const sr_dev_scene* sc, const float4* tb
     OrderArgs oa{nullptr, nullptr, (int)nblocks, fr->max_steps, 0, 6, fr->split_min_steps};
     hipLaunchKernelGGL(sr_shade_kernel<false>, dim3(grid.x, grid.y * B), block, 0, stream, sc, segs, bg, arr, *fr, ps,
                        ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa, (const int*)nullptr);
-    unsigned nb = (nblocks * B < SR_RESUME_TILES ? nblocks * B : SR_RESUME_TILES) * SR_WG_PER_TILE;
-    if (tr)
-        hipLaunchKernelGGL((sr_resume_kernel<true, true>), dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr,
-                           ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count);
-    else if (cull)
-        hipLaunchKernelGGL(sr_resume_kernel<true>, dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n,
-                           out, pitch, dbg_rgba, dbg_steps, list, count);
-    else
-        hipLaunchKernelGGL(sr_resume_kernel<false>, dim3(nb), dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n,
-                           out, pitch, dbg_rgba, dbg_steps, list, count);
+    launch_resume(tr, cull, nblocks * B, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list,
+                  count);
     return hipGetLastError();
 }
 

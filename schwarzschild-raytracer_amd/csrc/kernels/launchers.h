@@ -1,0 +1,71 @@
+// launchers.h — every extern "C" host entry the kernel files (*.hip) define
+// and the C ABI (sr_api.cpp) calls. Included from both sides, so the compiler
+// holds each definition to its declaration; a launcher is declared nowhere
+// else. The signatures are fixed: tools/build_variant.sh builds an earlier
+// revision's geodesic.hip against this tree.
+#ifndef SR_KERNELS_LAUNCHERS_H
+#define SR_KERNELS_LAUNCHERS_H
+
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "device_scene.h"
+
+extern "C" {
+
+// ---- geodesic.hip
+hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* tbl, const float* segs, const uint32_t* bg,
+                              const uint32_t* arr, const uint8_t* opq, const sr_dev_frame* fr, uint8_t* out,
+                              size_t pitch, float* dbg_rgba, int32_t* dbg_steps, float* ps, size_t ps_n, int* list,
+                              int* count, int* order, int* cost, int* diag, sr_dev_start* start, hipEvent_t* ev4,
+                              hipStream_t stream);
+// the shade and resume kernels alone, on pixel state a launch left (sr_reshade)
+hipError_t sr_launch_reshade(const sr_dev_scene* sc, const float4* tbl, const float* segs, const uint32_t* bg,
+                             const uint32_t* arr, const sr_dev_frame* fr, uint8_t* out, size_t pitch, float* dbg_rgba,
+                             int32_t* dbg_steps, float* ps, size_t ps_n, int* list, int* count, int* diag,
+                             hipStream_t stream);
+// one object code per pixel from that state (sr_pick_map)
+hipError_t sr_launch_pick(const sr_dev_scene* sc, const float* segs, const sr_dev_frame* fr, const float* ps,
+                          size_t ps_n, int32_t* out, size_t pitch, size_t frame_stride, hipStream_t stream);
+
+// ---- assemble.hip
+hipError_t sr_assemble_blocks_device(const uint8_t* stacked, size_t rank_stride, size_t in_frame_stride,
+                                     const int* dev_lists, int world, int per, int height, int block_rows,
+                                     size_t row_bytes, uint8_t* out, size_t out_frame_stride, int n_frames,
+                                     hipStream_t stream);
+int sr_assemble_blocks_host(const uint8_t* stacked, size_t rank_stride, size_t in_frame_stride, const int* lists,
+                            int world, int per, int height, int block_rows, size_t row_bytes, uint8_t* out,
+                            size_t out_frame_stride, int n_frames);
+
+// ---- resolve.hip
+hipError_t sr_resolve_box_device(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride, int width,
+                                 int rows, int ss, const int* dev_blocks, int block_rows, int height, uint8_t* out,
+                                 size_t pitch, size_t out_frame_stride, int n_frames, hipStream_t stream);
+hipError_t sr_resolve_box_masked_device(const uint8_t* samples, size_t sample_pitch, int width, int height, int ss,
+                                        const uint8_t* dev_mask, uint8_t* out, size_t pitch, hipStream_t stream);
+void sr_resolve_box_host(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride, int width, int rows,
+                         int ss, uint8_t* out, size_t pitch, size_t out_frame_stride, int n_frames);
+
+// ---- accum.hip
+hipError_t sr_accum_add_device(const uint8_t* images, size_t pitch, size_t image_stride, int n_images, int width,
+                               int rows, int reset, uint16_t* accum, size_t accum_pitch, hipStream_t stream);
+hipError_t sr_accum_resolve_device(const uint16_t* accum, size_t accum_pitch, int width, int rows, int n, uint8_t* out,
+                                   size_t pitch, hipStream_t stream);
+void sr_accum_add_host(const uint8_t* images, size_t pitch, size_t image_stride, int n_images, int width, int rows,
+                       int reset, uint16_t* accum, size_t accum_pitch);
+void sr_accum_resolve_host(const uint16_t* accum, size_t accum_pitch, int width, int rows, int n, uint8_t* out,
+                           size_t pitch);
+
+// ---- adaptive.hip
+hipError_t sr_edge_tiles_device(const uint8_t* img, size_t pitch, int width, int height, int threshold, int grow,
+                                uint8_t* dev_mask, hipStream_t stream);
+hipError_t sr_adaptive_codes_device(const uint8_t* dev_mask, int width, int height, int ss, const int* order,
+                                    int n_order, int* codes, uint8_t* user_mask, hipStream_t stream);
+void sr_edge_tiles_host(const uint8_t* img, size_t pitch, int width, int height, int threshold, int grow,
+                        uint8_t* mask);
+
+}  // extern "C"
+
+#endif

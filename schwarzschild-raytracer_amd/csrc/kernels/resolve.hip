@@ -26,6 +26,8 @@
 
 #include <cstdint>
 
+#include "launchers.h"
+
 namespace {
 
 constexpr int kThreads = 256;

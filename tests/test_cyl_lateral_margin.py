@@ -166,7 +166,7 @@ def test_cylinder_hits_stay_on_the_lateral_surface(radius):
     o = (tp - dn * lam0[:, None]).astype(F)
     seg32 = seg.astype(F)
     hit, p = cyl_test_f32(o, d, pos, c0, c1, c2, height, r, seg32)
-    # only orthonormal frames are budgeted or culled (sr_api.cpp orthonormal(),
+    # only orthonormal frames are budgeted or culled (precompute.cpp orthonormal(),
     # tolerance 1e-5: the reference's gram_schmidt of d.xzy, d, d.zxy is
     # ill-conditioned for some axes, and such objects stay exact)
     hit &= orthonormal_f32(c0, c1, c2)
@@ -180,7 +180,7 @@ def test_cylinder_hits_stay_on_the_lateral_surface(radius):
     # near-parallel chords are among the accepted ones (the case the old margin priced by 1 / |d_perp|^2)
     assert (theta[hit] < 1e-3).sum() > 100
     # the length-aware form, in the frame's coordinates (the world distance
-    # scales by the bound's |M^-1| |M|^2, sr_api.cpp frame_norms)
+    # scales by the bound's |M^-1| |M|^2, precompute.cpp frame_norms)
     fdev = frame_lateral_dev(p[hit], pos[hit], c0[hit], c2[hit], r[hit])
     ratio_len = fdev / lat_margin_len(seg32[hit].astype(np.float64), sc, radius)
     assert ratio_len.max() < 0.1, (ratio_len.max(), int(np.argmax(ratio_len)))
@@ -239,7 +239,7 @@ def test_skewed_frames_scale_the_lateral_margin(radius, capsys):
     numbers up to ~1e6. cyl_test then tests the M^-1 image of the frame's
     cylinder, and tr_bound_may_hit / clearance_tr (geodesic.hip) assume that
     an accepted point lies within lat_margin_len(len, Sc, r) x |M^-1| |M|^2
-    of that image's lateral surface (spectral norms, sr_api.cpp frame_norms;
+    of that image's lateral surface (spectral norms, precompute.cpp frame_norms;
     len, Sc of the chord in world coordinates). Grazing chords at every
     angle to the axis are built in the frame's coordinates and mapped back
     through M^-1; every accepted point's binary64 distance from the image

@@ -532,7 +532,7 @@ def test_cameras_near_the_horizon(gpu, wd, key, cam, cull):
 def test_arguments_rejected_on_a_live_context(gpu, wd):
     """Each bad call returns SR_E_INVALID before any launch (sr_api.cpp:
     sr_render / sr_render_blocks_batch / sr_render_block_list check their
-    own arguments, build_frame the params, launch() pitch and frame stride,
+    own arguments, build_frame the params, the pitch and the frame stride,
     all ahead of the first stream operation), writes nothing, and leaves the
     context as it was: the good render repeats byte for byte."""
     import torch

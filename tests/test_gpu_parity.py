@@ -448,7 +448,7 @@ def test_random_scenes_culling_exact(pkg, gpu, seed):
 def test_skewed_frames_budgeted(pkg, gpu, oracle, oracle_tex, shear, scale):
     """Rectangles and boxes whose frames are not orthonormal (a column scaled,
     a shear between columns) are budgeted by the bounding sphere of their
-    faces' parallelograms since round 6 (sr_api.cpp parallelogram_corners;
+    faces' parallelograms since round 6 (precompute.cpp parallelogram_corners;
     they were tested on every chord and turned lazy chords off for the whole
     frame): the default scene with its rectangle and box so skewed, whole
     frames bit-exact against the oracle, and culling on vs off identical."""
@@ -941,13 +941,13 @@ def test_objects_near_orbital_planes(pkg, gpu, oracle, oracle_tex, u_f):
     (0.01, 100, 7.0, 2.9, 2), (0.01, 100, 7.0, 3.4, 3), (0.01, 8000, 7.0, 2.9, 2), (0.01, 300, 4.0, 2.7, 1)])
 def test_cylinder_near_orbital_planes(pkg, gpu, oracle, oracle_tex, u_f, max_steps, t, d, revs):
     """The cylinder's orbital-plane exclusion for low-energy orbits
-    (geodesic.hip SR_XCYL, sr_api.cpp xcyl_need: about br + 0.3 at the
+    (geodesic.hip SR_XCYL, precompute.cpp xlow_need: about br + 0.3 at the
     default step angle and u_f = 0.01, +inf at u_f = 1e-4). Every orbital
     plane holds the line through the camera and the hole; the cylinder's
     base sits at t along it and d off it, so its bounding centre is at 0 ..
     d + 2 from the planes of the frame's rays, across the exclusion's
     threshold. Step angles over the range the exclusions are enabled for
-    (sr_api.cpp clear_radius, SR_XLOW_DPHI_MAX; tests/test_low_energy_bounds.py
+    (precompute.cpp clear_radius, SR_XLOW_DPHI_MAX; tests/test_low_energy_bounds.py
     proves the premises there): the app's MAX_STEPS 100 (src/main.cpp:68) at
     two and three revolutions (0.126, 0.188 rad), 300 steps at one, 600 and
     1200 at two, and config 5's 8000; whole 160x90 frames, bit-exact with
@@ -969,7 +969,7 @@ def test_cylinder_near_orbital_planes(pkg, gpu, oracle, oracle_tex, u_f, max_ste
     (0.01, 1200, 3.2, 4.0, 2), (0.01, 600, 4.5, 5.5, 2), (0.05, 1200, 2.6, 6.5, 2), (1.0e-4, 1200, 3.2, 4.0, 2),
     (0.01, 100, 3.2, 4.0, 2), (0.01, 100, 4.5, 5.5, 3), (0.01, 8000, 3.2, 4.0, 2), (0.01, 300, 2.6, 6.5, 1)])
 def test_objects_near_periapsis(pkg, gpu, oracle, oracle_tex, u_f, max_steps, rs, rb, revs):
-    """The periapsis exclusion (geodesic.hip SR_XPERI, sr_api.cpp xperi_e): a
+    """The periapsis exclusion (geodesic.hip SR_XPERI, precompute.cpp xperi_e): a
     low-energy orbit never comes closer to the hole than its periapsis, so
     objects whose reachable chords all lie inside that sphere are excluded
     for it. A sphere and a box moved close to the hole (centres at rs and rb

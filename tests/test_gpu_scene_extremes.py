@@ -26,7 +26,7 @@ with culling off, which equalled the oracle everywhere): disk_radius_neg4
 607 at 400 steps and 592 at 100, alone and embedded (every pixel that shows
 the disk); annulus_neg_neg and annulus_pos_neg 147 alone, 139 and 138
 embedded; annulus_neg_pos and every other case 0. The distance-to-primitive
-clearance took rho - radius with the signed radius (sr_api.cpp pack_slot now
+clearance took rho - radius with the signed radius (precompute.cpp pack_slot now
 stores magnitudes).
 """
 import ctypes as C

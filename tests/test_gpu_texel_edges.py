@@ -1,7 +1,7 @@
 """The step loop's opacity classification at texel-scale alpha edges.
 
 hit_opacity_uniform (geodesic.hip) ends a ray at a textured hit when a
-per-texel bitmap built at upload (sr_api.cpp make_opacity_map: every texel
+per-texel bitmap built at upload (precompute.cpp opacity_bits: every texel
 within SR_OPQ_RADIUS = 2 of this one, wrapping like the sampler, has alpha
 255) says the bilinear footprint reads alpha 1 exactly; it locates the
 footprint with a binary32 approximation of the shaded uv. The other suites'

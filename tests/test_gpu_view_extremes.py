@@ -74,7 +74,7 @@ oracle):
 - every other cell, finite or not, every batch frame, every launch option
   and every sample mapping: 0.
 Launches with max_revolutions <= 0, u_f < 0, u_f = -0.0 or NaN now run the
-culling-off instantiation (sr_api.cpp build_frame).
+culling-off instantiation (precompute.cpp derive_frame).
 """
 import contextlib
 

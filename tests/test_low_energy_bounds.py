@@ -1,9 +1,9 @@
 """The premises of the low-energy exclusions (geodesic.hip SR_XCYL /
-SR_XPERI, sr_api.cpp clear_radius / xlow_need / xperi_e), checked on the
+SR_XPERI, csrc/host/precompute.cpp clear_radius / xlow_need / xperi_e), checked on the
 kernel's own integrator arithmetic over every step angle the exclusions are
-enabled for (sr_api.cpp clear_radius: max_dphi <= SR_XLOW_DPHI_MAX = 0.2,
-device_scene.h): the host's 16-byte step table in binary32 (sr_api.cpp
-ensure_table: step_i = (max_angle - phi) / (N - i), frag:914-915) and
+enabled for (precompute.cpp clear_radius: max_dphi <= SR_XLOW_DPHI_MAX = 0.2,
+device_scene.h): the host's 16-byte step table in binary32 (precompute.cpp
+step_table: step_i = (max_angle - phi) / (N - i), frag:914-915) and
 geodesic.hip rk4_step's binary32 operation order (fma(0.5, q h, a) half
 steps, fma(2, k3, fma(2, k2, k1)) sums; every fma here adds an exact product,
 so the numpy float32 expressions below round exactly as the kernel does).
@@ -26,7 +26,7 @@ import pytest
 
 EMAX = np.float32(0.14)  # device_scene.h SR_XCYL_EMAX
 DPHI_CAP = np.float32(0.2)  # device_scene.h SR_XLOW_DPHI_MAX
-PI = np.float32(3.1415926535)  # sr_api.cpp kPi (the shader's PI, frag:860)
+PI = np.float32(3.1415926535)  # precompute.cpp kPi (the shader's PI, frag:860)
 f32 = np.float32
 
 
@@ -46,7 +46,8 @@ def u_turn(E):
 
 
 def step_table(max_steps: int, max_revs: int) -> np.ndarray:
-    """sr_api.cpp ensure_table's step sizes, binary32 (cos / sin not needed)."""
+    """precompute.cpp step_table's step sizes, binary32 (cos / sin not needed;
+    tests/test_host_precompute.py holds the library's table to this one bit for bit)."""
     max_angle = f32(2.0) * f32(max_revs) * PI
     phi = f32(0.0)
     h = np.empty(max_steps, dtype=f32)
@@ -58,7 +59,8 @@ def step_table(max_steps: int, max_revs: int) -> np.ndarray:
 
 
 def max_dphi(max_steps: int, max_revs: int) -> float:
-    """sr_api.cpp build_frame's out_dip and max_dphi."""
+    """precompute.cpp derive_frame's out_dip and max_dphi (held to the library's
+    by tests/test_host_precompute.py)."""
     max_angle = float(f32(2.0) * f32(max_revs) * PI)
     dphi = max_angle / max_steps
     out_dip = f32(1.0 - dphi * dphi / 8.0 - 1e-6)
@@ -145,7 +147,8 @@ def test_step_angle_cap_matches_the_library():
     h = (Path(__file__).resolve().parent.parent / "schwarzschild-raytracer_amd" / "csrc" / "device_scene.h").read_text()
     m = re.search(r"#define SR_XLOW_DPHI_MAX ([0-9.]+)f", h)
     assert m and f32(float(m.group(1))) == DPHI_CAP
-    api = (Path(__file__).resolve().parent.parent / "schwarzschild-raytracer_amd" / "csrc" / "sr_api.cpp").read_text()
+    api = (Path(__file__).resolve().parent.parent / "schwarzschild-raytracer_amd" / "csrc" / "host" /
+           "precompute.cpp").read_text()
     assert "max_dphi <= SR_XLOW_DPHI_MAX" in api
     # schedules just beyond the cap are excluded from the proof and from the library
     assert max_dphi(94, 3) > DPHI_CAP and max_dphi(95, 3) <= DPHI_CAP

@@ -68,7 +68,7 @@ def test_table_shape():
                     if c.group == "split" and params_value(c, "raytrace_type") == t], [-0.5, 0.0, 1.0, 1.5, V.NAN])
     assert has(values("noise", "percent_black"), [0.0, 0.5, 1.0, 2.0, V.NAN])
     assert any(params_value(c, "max_steps") == 65536 and c.size == (16, 8) for c in V.CASES)
-    # the cameras at r = 100: the host's own sum (sr_api.cpp launch: doubles, <= 1e4)
+    # the cameras at r = 100: the host's own sum (precompute.cpp derive_frame: doubles, <= 1e4)
     r2 = {n: sum(float(np.float32(v)) ** 2 for v in V.BY_NAME[n].pos)
           for n in ("uf_0p01_r100", "uf_0p01_r100_up", "uf_0p01_r100_down")}
     assert r2["uf_0p01_r100_down"] < r2["uf_0p01_r100"] == 1.0e4 < r2["uf_0p01_r100_up"]

@@ -20,10 +20,11 @@ $H $FLAGS --offload-arch=gfx950 -fno-gpu-rdc -x hip -c $PKG/csrc/kernels/resolve
 $H $FLAGS --offload-arch=gfx950 -fno-gpu-rdc -x hip -c $PKG/csrc/kernels/adaptive.hip -o $OBJ/adaptive.o &
 $H $FLAGS --offload-arch=gfx950 -fno-gpu-rdc -x hip -c $PKG/csrc/kernels/accum.hip -o $OBJ/accum.o &
 $H $FLAGS "$@" -c $PKG/csrc/sr_api.cpp -o $OBJ/sr_api.o &
+$H $FLAGS "$@" -c $PKG/csrc/host/precompute.cpp -o $OBJ/precompute.o &
 $H $FLAGS -c $PKG/csrc/host/scene.cpp -o $OBJ/scene.o &
 $H $FLAGS -c $PKG/csrc/host/png.cpp -o $OBJ/png.o &
 $H $FLAGS -c $PKG/csrc/host/partition.cpp -o $OBJ/partition.o &
 wait
-$H -shared --offload-arch=gfx950 -Wl,-Bsymbolic -o $OUT/libsr_$NAME.so $OBJ/geodesic.o $OBJ/assemble.o $OBJ/resolve.o $OBJ/adaptive.o $OBJ/accum.o $OBJ/sr_api.o $OBJ/scene.o $OBJ/png.o $OBJ/partition.o -lz
+$H -shared --offload-arch=gfx950 -Wl,-Bsymbolic -o $OUT/libsr_$NAME.so $OBJ/geodesic.o $OBJ/assemble.o $OBJ/resolve.o $OBJ/adaptive.o $OBJ/accum.o $OBJ/sr_api.o $OBJ/precompute.o $OBJ/scene.o $OBJ/png.o $OBJ/partition.o -lz
 $H $FLAGS --offload-arch=gfx950 "$@" -x hip --cuda-device-only -S "$KSRC" -o $OBJ/geodesic.s
 echo "$NAME: $(grep -E '^\s+\.(vgpr_count|sgpr_count|vgpr_spill_count)' $OBJ/geodesic.s | head -3 | tr -s ' ' | tr '\n' ' ')"
