@@ -742,6 +742,74 @@ int sr_get_projection(sr_ctx* ctx);
  * output, sizes <= 0 or above INT32_MAX / 2, or a pixel off the frame. */
 int sr_projection_dir(int projection, float fov, int uv_width, int uv_height, int px, int py, float out_local[3]);
 
+/* ---- Scene sequences (not in the reference, which uploads its one scene per
+ * draw call). The frames of a batched launch (sr_render_blocks_batch,
+ * sr_render_block_list) differ only in the camera; an animation in which
+ * anything of the scene moves would be a loop of sr_set_scene and sr_render,
+ * every frame alone behind a host wait. A sequence holds the animation's
+ * scenes on the device, and one launch renders up to 32 frames from
+ * consecutive scenes of it, each frame with a camera of its own.
+ *
+ * Definition. Frame f of a sequence launch holds exactly the bytes sr_render
+ * (with ss > 1: sr_render_ss) writes for cams[f] on a context whose scene is
+ * scenes[first_scene + f], given the same background, texture array, test
+ * ray, projection, params and settings. Layout, pitch, frame stride, the
+ * block list's -1 padding and the rows left unwritten are those of
+ * sr_render_blocks_batch (one band of rows) and sr_render_block_list(_ss). The
+ * launch is asynchronous on `stream` with no host wait, ordered like every
+ * launch of the context, and learns and uses the launch order of its grid
+ * shape as a batch does.
+ *
+ * The sequence and the context's own scene (sr_set_scene) are independent
+ * states: neither call touches the other's scene or drops the other's
+ * retained frame, and a sequence launch does not need sr_set_scene.
+ * sr_set_test_ray packs the test-ray part of every scene of the sequence
+ * again; sr_set_background, sr_set_texture_array, sr_set_projection,
+ * sr_set_split and culling apply to sequence launches as to any launch. The
+ * test-ray overlay is tested per chord (as under a projection), and the
+ * latency mode (sr_set_latency_mode) runs the default unroll under sequences;
+ * the pixels are the same either way. The integrate kernel's slot capacity
+ * is chosen per launch for the largest scene of the launch's window.
+ *
+ * A sequence launch leaves no retained frame ("the context's current scene"
+ * has no meaning for it): sr_can_reshade is 0, and sr_reshade,
+ * sr_reshade_debug and sr_pick_map return SR_E_NOT_READY until the next plain
+ * launch. Sample phases, sr_render_adaptive and sr_wave_costs have no
+ * sequence form; to price a rank's block lists use sr_set_scene with one
+ * scene of the sequence. */
+#define SR_MAX_SEQUENCE 256
+/* Snapshot copies of n scenes (1 .. SR_MAX_SEQUENCE), each validated and
+ * packed as sr_set_scene does with the context's current test ray, uploaded
+ * as one array (14,652 bytes per scene). Synchronous like sr_set_scene
+ * (waits for the context's frames). Replaces an earlier sequence; n == 0
+ * clears it. SR_E_CAPACITY above SR_MAX_SEQUENCE; when scene k is rejected,
+ * its status (SR_E_INVALID, SR_E_CAPACITY) and the earlier sequence stays in
+ * force. SR_E_INVALID for a null context, n < 0 or null scenes with n > 0. */
+int sr_set_scene_sequence(sr_ctx* ctx, const sr_scene* scenes, int n);
+/* scenes in the context's sequence (0: none); SR_E_INVALID for a null context */
+int sr_scene_sequence_length(sr_ctx* ctx);
+/* Rows [row_begin, row_end) of n_frames frames, frame f from scene
+ * first_scene + f and cams[f], at dev_rgba8 + f * frame_stride_bytes; ss in
+ * 1 .. SR_MAX_SUPERSAMPLE (box-filtered as sr_render_ss). Nothing is launched
+ * or written on a rejection: SR_E_NOT_READY without a sequence; SR_E_INVALID
+ * when [first_scene, first_scene + n_frames) leaves the sequence;
+ * SR_E_CAPACITY above 32 frames; otherwise those of sr_render(_ss) and of
+ * sr_render_blocks_batch's frame stride. */
+int sr_render_sequence(sr_ctx* ctx, int first_scene, const sr_camera* cams, int n_frames,
+                       const sr_params* params, int width, int height, int row_begin, int row_end, int ss,
+                       uint8_t* dev_rgba8, size_t pitch_bytes, size_t frame_stride_bytes, sr_stream stream);
+/* The same for the blocks of a list (-1: padding, its rows unwritten), as
+ * sr_render_block_list(_ss), whose rejections it adds to the above. */
+int sr_render_sequence_block_list(sr_ctx* ctx, int first_scene, const sr_camera* cams, int n_frames,
+                                  const sr_params* params, int width, int height, int block_rows,
+                                  const int* blocks, int n_blocks, int ss, uint8_t* dev_rgba8,
+                                  size_t pitch_bytes, size_t frame_stride_bytes, sr_stream stream);
+/* sr_render_debug of one scene of the sequence: float FragColor, RGBA8 and
+ * the executed steps of rows [row_begin, row_end) (any of the three null) */
+int sr_render_sequence_debug(sr_ctx* ctx, int scene_index, const sr_camera* cam, const sr_params* params,
+                             int width, int height, int row_begin, int row_end, float* dev_rgba32,
+                             uint8_t* dev_rgba8, int32_t* dev_steps, sr_stream stream);
+
 /* Rows a sr_render_blocks call with these arguments writes. */
 int sr_blocks_row_count(int height, int block_rows, int block_first, int block_step);
 

@@ -223,6 +223,13 @@ SIGNATURES = {
     "sr_set_projection": (_i, [_p, _i]),
     "sr_get_projection": (_i, [_p]),
     "sr_projection_dir": (_i, [_i, C.c_float, _i, _i, _i, _i, C.POINTER(C.c_float)]),
+    "sr_set_scene_sequence": (_i, [_p, C.POINTER(Scene), _i]),
+    "sr_scene_sequence_length": (_i, [_p]),
+    "sr_render_sequence": (_i, [_p, _i, C.POINTER(Camera), _i, C.POINTER(Params), _i, _i, _i, _i, _i, _p, C.c_size_t,
+                                C.c_size_t, _p]),
+    "sr_render_sequence_block_list": (_i, [_p, _i, C.POINTER(Camera), _i, C.POINTER(Params), _i, _i, _i, C.POINTER(_i),
+                                           _i, _i, _p, C.c_size_t, C.c_size_t, _p]),
+    "sr_render_sequence_debug": (_i, [_p, _i, C.POINTER(Camera), C.POINTER(Params), _i, _i, _i, _i, _p, _p, _p, _p]),
 }
 # sr_set_projection's values (sr.h "Projections")
 PROJECTION_RECTILINEAR, PROJECTION_EQUIRECT, PROJECTION_FISHEYE = 0, 1, 2
@@ -230,6 +237,9 @@ PROJECTIONS = {"rectilinear": PROJECTION_RECTILINEAR, "equirect": PROJECTION_EQU
 # header functions a library built from an earlier revision lacks (the parent
 # build of an A/B timing, tools/bench_ab.sh): such a library still loads
 SINCE_PROJECTIONS = ("sr_set_projection", "sr_get_projection", "sr_projection_dir")
+SINCE_SEQUENCES = ("sr_set_scene_sequence", "sr_scene_sequence_length", "sr_render_sequence",
+                   "sr_render_sequence_block_list", "sr_render_sequence_debug")
+MAX_SEQUENCE = 256  # scenes of a sequence (sr.h "Scene sequences")
 # sr_pick_map's codes below the indices into scene.objects[]
 PICK_SKY, PICK_HOLE, PICK_TEST_RAY_FLAT, PICK_TEST_RAY_CURVED, PICK_NONE = -1, -2, -3, -4, -5
 MAX_SUPERSAMPLE = 4
@@ -275,7 +285,7 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         raise FileNotFoundError(f"{p} not built; run __graft_entry__.build() or make -C schwarzschild-raytracer_amd")
     lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **EXTRA_SIGNATURES}.items():
-        if (name in EXTRA_SIGNATURES or name in SINCE_PROJECTIONS) and not hasattr(lib, name):
+        if (name in EXTRA_SIGNATURES or name in SINCE_PROJECTIONS or name in SINCE_SEQUENCES) and not hasattr(lib, name):
             continue  # debug tooling and newer calls an older library (a bisection build) may lack
         fn = getattr(lib, name)
         fn.restype = res

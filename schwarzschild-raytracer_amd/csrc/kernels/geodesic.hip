@@ -961,6 +961,30 @@ __device__ __forceinline__ void budget_frame(const sr_dev_scene* __restrict__ sc
 #endif
     bs.setCm(cm, x);
 }
+// budget_frame of a sequence launch's integrate kernel (sr.h "Scene
+// sequences"): the frame struct holds no exclusions there (the frames' scenes
+// differ), the low-energy ones of the frame's own scene are in its start
+// record (sr_start_table_seq_kernel). A copy and not a parameter of
+// budget_frame: the frame kernels' code stays the parent's to the byte.
+template <class BS>
+__device__ __forceinline__ void budget_frame_seq(const sr_dev_scene* __restrict__ sc, BS& bs, f3 nv, f3 tv, float xs,
+                                                 const sr_dev_start_slot* __restrict__ xslot, float eo) {
+    const uint32_t cm = budget_cyl_frame(sc, bs, nv, tv);
+    uint32_t x = 0;
+#if SR_XPLANE
+    {
+        const f3 n = cross(nv, tv);
+        const float nn = dot(n, n);
+        const int nb = sc->num_budget;
+        for (int j = 1; j <= nb; j++) {
+            x |= xplane_bit(sc->slots[j - 1], j, n, nn, xs);
+            if (SR_XCYL && eo <= SR_XCYL_EMAX) x |= xcyl_bit(sc->slots[j - 1], j, n, nn, xslot[j - 1].xneed);
+            if (SR_XPERI && eo <= xslot[j - 1].xperi) x |= 1u << j;
+        }
+    }
+#endif
+    bs.setCm(cm, x);
+}
 
 // bs.cm's bit for slot j (budgeted cylinders; false for other slots)
 template <class BS>
@@ -2576,8 +2600,11 @@ __device__ __forceinline__ bool certain_end(float u, float up, float r2) {
 // sr_wave_costs: budget events of each wave of the integrate kernel's workgroup
 __shared__ int sr_lds_ev[SR_WG / 64];
 
+// SEQ (with RECORD): a sequence launch's integrate kernel; sc is the frame's
+// own scene, whose slot count and low-energy exclusions (the start record's)
+// stand where the frame struct's do otherwise.
 template <bool CULL, bool RECORD, bool WCOST = false, int NB = SR_MAX_BUDGET, int FU = SR_FAST_UNROLL,
-          int NC = SR_NC_KERNEL, bool TR = false>
+          int NC = SR_NC_KERNEL, bool TR = false, bool SEQ = false>
 __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, const float* __restrict__ segs,
                                          const float4* __restrict__ tbl, const sr_dev_frame& fr, const Tex& tx,
                                          Ray& r, Hit& hit, HitLog& log, const sr_dev_start* __restrict__ start = nullptr) {
@@ -2590,7 +2617,7 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
     if constexpr (CULL && RECORD)
         // the ray's start (sr_integrate_kernel) at the camera, from the frame's
         // start record; r.rd is the orbit's tangent at r.ro
-        budget_start(sc, *start, bs, fr.num_budget, r.ro, r.nv, r.tv, r.du < 0.0f && r.u < 0.6f, r.du > 0.0f,
+        budget_start(sc, *start, bs, SEQ ? sc->num_budget : fr.num_budget, r.ro, r.nv, r.tv, r.du < 0.0f && r.u < 0.6f, r.du > 0.0f,
                      orbit_e(r.u, r.du), r.rd);
     else if (CULL)
         // a resumed ray's r.rd is a chord direction, so no start window. (Round
@@ -2678,7 +2705,9 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         r.tv = nrm(cross(cross(r.nv, r.rd), r.nv));
         r.u = 1.0f / len(q);
         r.du = -r.u * dot(r.rd, r.nv) / dot(r.rd, r.tv);
-        if (CULL) budget_frame(sc, bs, r.nv, r.tv, fr.xplane_s, fr.xlow_need, fr.xperi_e,
+        if constexpr (CULL && RECORD && SEQ)
+            budget_frame_seq(sc, bs, r.nv, r.tv, fr.xplane_s, start->slot, orbit_e(r.u, r.du));
+        else if (CULL) budget_frame(sc, bs, r.nv, r.tv, fr.xplane_s, fr.xlow_need, fr.xperi_e,
                                   orbit_e(r.u, r.du));
         force = true;  // the chord starts at the exact r.ro
         return -1;
@@ -3284,6 +3313,29 @@ __global__ __launch_bounds__(64) void sr_start_table_kernel(const sr_dev_scene* 
     build_start(sc, segs, fr, ld3(fr.cam[f].pos), start[f]);
 }
 
+// Floats per scene of a sequence launch's exclusion table (sr_api.cpp
+// ensure_xtab): xlow_need, then xperi_e, of every budget slot
+#define SR_XTAB_FLOATS (2 * SR_MAX_BUDGET)
+// The start table of a sequence launch (sr.h "Scene sequences"): frame f's
+// record from its own scene sc[f]. The frame struct holds no low-energy
+// exclusions (build_start writes +inf / -1); the scene's own, for the
+// launch's (u_f, step angle), come from the host's table.
+__global__ __launch_bounds__(64) void sr_start_table_seq_kernel(const sr_dev_scene* __restrict__ sc,
+                                                                const float* __restrict__ segs, sr_dev_frame fr,
+                                                                sr_dev_start* __restrict__ start,
+                                                                const float* __restrict__ xtab) {
+    const int f = (int)blockIdx.x;
+    if (f >= fr.batch || threadIdx.x != 0) return;
+    build_start(sc + f, segs, fr, ld3(fr.cam[f].pos), start[f]);
+    int nb = sc[f].num_budget;
+    nb = nb < SR_MAX_BUDGET ? nb : SR_MAX_BUDGET;
+    const float* const x = xtab + (size_t)f * SR_XTAB_FLOATS;
+    for (int j = 0; j < nb; j++) {
+        start[f].slot[j].xneed = x[j];
+        start[f].slot[j].xperi = x[SR_MAX_BUDGET + j];
+    }
+}
+
 // 1-D grid: workgroup s = (slot * B + f) * SR_WG_PER_TILE + part renders
 // part `part` (SR_WG threads) of launch code order[slot] of frame f of the
 // batch (costliest tiles of every frame first, order_tiles), and records
@@ -3297,8 +3349,10 @@ __global__ __launch_bounds__(64) void sr_start_table_kernel(const sr_dev_scene* 
 // TR: the test-ray instantiation (the test ray budgeted, clearance_tr)
 // PROJ: the projection (init_pixel); the angular ones have instantiations of
 // their own (sr_launch_projected), the rectilinear ones are untouched by them
+// SEQ: a sequence launch's instantiation (sr_launch_geodesic_seq): sc is an
+// array, frame f reads sc[f]
 template <bool CULL, bool WCOST = false, int NB = SR_MAX_BUDGET, int FU = SR_FAST_UNROLL, int NC = SR_NC_KERNEL,
-          bool TR = false, int PROJ = SR_PROJECTION_RECTILINEAR>
+          bool TR = false, int PROJ = SR_PROJECTION_RECTILINEAR, bool SEQ = false>
 __global__ __launch_bounds__(SR_WG, sr_integrate_waves(NB, NC)) void sr_integrate_kernel(
     const sr_dev_scene* __restrict__ sc, const float4* __restrict__ tbl, const float* __restrict__ segs,
     const uint32_t* __restrict__ arr, const uint8_t* __restrict__ opq, sr_dev_frame fr, float* __restrict__ ps_base,
@@ -3344,7 +3398,9 @@ __global__ __launch_bounds__(SR_WG, sr_integrate_waves(NB, NC)) void sr_integrat
         int st = init_pixel<PROJ>(fr, fr.cam[frame], PROJ != SR_PROJECTION_RECTILINEAR ? fr.cam_a[frame] : 0.0f,
                                   start[frame], q, r);
         SR_PROBE(st = wp.lane_mask(q.px, q.py, fr.width, st, ST_DONE); wp.ray_start(r));
-        if (st < 0) st = integrate<CULL, true, WCOST, NB, FU, NC, TR>(sc, segs, tbl, fr, tx, r, hit, log, start + frame);
+        if (st < 0)
+            st = integrate<CULL, true, WCOST, NB, FU, NC, TR, SEQ>(SEQ ? sc + frame : sc, segs, tbl, fr, tx, r, hit, log,
+                                                                   start + frame);
         const size_t id = log.id();
         ps.put_rec(id, ps_word(st, log.n, r.steps), r.rd);
         SR_PROBE(wp.pixel(st, log.n));
@@ -3467,7 +3523,8 @@ struct OrderArgs {
 #endif
 // SPARSE: the sparse launch's instantiation (`codes`, sr_launch_geodesic); every
 // other launch runs <false>, whose code has no trace of the list
-template <bool SPARSE>
+// SEQ: a sequence launch's instantiation (sc an array: frame f shades with sc[f])
+template <bool SPARSE, bool SEQ = false>
 __global__ __launch_bounds__(256, SR_SHADE_WAVES_PER_EU) void sr_shade_kernel(const sr_dev_scene* __restrict__ sc,
                                                       const float* __restrict__ segs,
                                                       const uint32_t* __restrict__ bg,
@@ -3493,6 +3550,7 @@ __global__ __launch_bounds__(256, SR_SHADE_WAVES_PER_EU) void sr_shade_kernel(co
         vblock = code >> 8;
     }
     const int f = vblock / fr.tiles, block = vblock - f * fr.tiles;
+    if constexpr (SEQ) sc += f;
     Pix q;
     if (!pixel_of(fr, block, threadIdx.x, q)) return;
     const size_t id = (size_t)vblock * 256 + threadIdx.x;
@@ -3551,7 +3609,12 @@ __global__ __launch_bounds__(256, SR_SHADE_WAVES_PER_EU) void sr_shade_kernel(co
     write_pixel(fr, out, pitch, dbg_rgba, dbg_steps, q, frag, steps_at);
 }
 
-template <bool CULL, bool TR = false>
+// SEQ: a sequence launch's instantiation (sc an array). A wave's rays come
+// from the worklist in any order, so their frames differ: the wave runs the
+// rounds once per frame of the batch, for the lanes of that frame, with the
+// frame's scene as a wave-uniform pointer (the scene reads stay scalar
+// loads). A ray's result does not depend on its wave-mates.
+template <bool CULL, bool TR = false, bool SEQ = false>
 __global__ __launch_bounds__(SR_WG) void sr_resume_kernel(const sr_dev_scene* __restrict__ sc,
                                                        const float4* __restrict__ tbl,
                                                        const float* __restrict__ segs,
@@ -3562,6 +3625,7 @@ __global__ __launch_bounds__(SR_WG) void sr_resume_kernel(const sr_dev_scene* __
                                                        float* __restrict__ dbg_rgba, int32_t* __restrict__ dbg_steps,
                                                        const int* __restrict__ list, const int* __restrict__ count) {
     const int total = *count;
+    const sr_dev_scene* const scenes = sc;  // SEQ: sc becomes each ray's frame's below
     const PS ps{ps_base, ps_n};
     Tex tx;
     tx.bg = bg;
@@ -3584,19 +3648,30 @@ __global__ __launch_bounds__(SR_WG) void sr_resume_kernel(const sr_dev_scene* __
         r.i = ps.geti(PS_I, id) + 1;
         r.steps = (int)((unsigned)__float_as_int(rec.x) >> 8);
         HitLog log{ps, 0};  // RECORD = false: nothing is logged
-        for (;;) {  // rounds: integrate to the next hit, shade, resume if not opaque
-            Hit hit = no_hit();
-            const int st = integrate<CULL, false, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, TR>(
-                sc, segs, tbl, fr, tx, r, hit, log);
-            if (st == ST_HIT) {
-                f4 c = shade(sc, fr, tx, hit, -r.rd);
-                frag = frag + c;
-                if (c.w == 1.0f) break;  // frag:932
-                r.i++;
-                continue;
+        // SEQ: one pass per frame of the batch, for the lanes whose ray is
+        // that frame's, with its scene (a wave-uniform loop: the lanes stay
+        // together; the index is read back from the lanes that agree, as
+        // inside that branch the compiler may put f, a vector value, for
+        // fu); otherwise the one pass
+        for (int fu = 0; fu < (SEQ ? fr.batch : 1); fu++) {
+            if constexpr (SEQ) {
+                if (f != fu) continue;
+                sc = scenes + __builtin_amdgcn_readfirstlane(f);
             }
-            finish_ray(sc, segs, fr, tx, st, r.ro, r.rd, frag);
-            break;
+            for (;;) {  // rounds: integrate to the next hit, shade, resume if not opaque
+                Hit hit = no_hit();
+                const int st = integrate<CULL, false, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, TR>(
+                    sc, segs, tbl, fr, tx, r, hit, log);
+                if (st == ST_HIT) {
+                    f4 c = shade(sc, fr, tx, hit, -r.rd);
+                    frag = frag + c;
+                    if (c.w == 1.0f) break;  // frag:932
+                    r.i++;
+                    continue;
+                }
+                finish_ray(sc, segs, fr, tx, st, r.ro, r.rd, frag);
+                break;
+            }
         }
         const size_t fo = (size_t)f * (size_t)fr.width * (size_t)fr.nrows;
         write_pixel(fr, out ? out + (size_t)f * (size_t)fr.out_frame_stride : nullptr, pitch,
@@ -3866,5 +3941,92 @@ extern "C" hipError_t sr_launch_pick(const sr_dev_scene* sc, const float* segs, 
     if (!ps || !out) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sr_pick_kernel<0>, dim3(grid.x, grid.y * B), dim3(256), 0, stream, sc, segs, *fr, ps, ps_n, out,
                        pitch, frame_stride);
+    return hipGetLastError();
+}
+
+// ---- scene sequences (sr.h): one launch whose frame f reads the scene sc[f]
+
+// The sequence integrate kernel of a launch's kind, three per projection:
+// culling off (the reference's loop), the small layout (every scene of the
+// window fits SR_NB_SMALL slots and SR_NC_SMALL cylinders: fr.num_budget and
+// fr.num_budget_cyl are the window's maxima) and all slots. The overlay is
+// tested per chord (TR = false, as in the projected launches); the latency
+// mode's unroll is not instantiated (the default unroll, the same pixels).
+template <int PROJ>
+static void launch_integrate_seq(bool cull, bool small, dim3 grid, hipStream_t stream, const sr_dev_scene* sc,
+                                 const float4* tbl, const float* segs, const uint32_t* arr, const uint8_t* opq,
+                                 const sr_dev_frame& fr, float* ps, size_t ps_n, int* count, int* order, int* cost,
+                                 sr_dev_start* start) {
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost,
+                           start);
+    };
+    if (!cull)
+        go(sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1, false, PROJ, true>);
+    else if (small)
+        go(sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, false, PROJ, true>);
+    else
+        go(sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ, true>);
+}
+
+// sr_launch_geodesic for the frames of a scene sequence: sc[f] is frame f's
+// scene (fr->batch of them), xtab their low-energy exclusions for the launch's
+// (u_f, step angle), SR_XTAB_FLOATS floats per scene. fr->num_budget and
+// fr->num_budget_cyl are the maxima over sc[0 .. batch), fr's own exclusions
+// "none". No sparse launch, no wave costs.
+extern "C" hipError_t sr_launch_geodesic_seq(const sr_dev_scene* sc, const float* xtab, const float4* tbl,
+                                             const float* segs, const uint32_t* bg, const uint32_t* arr,
+                                             const uint8_t* opq, const sr_dev_frame* fr, uint8_t* out, size_t pitch,
+                                             float* dbg_rgba, int32_t* dbg_steps, float* ps, size_t ps_n, int* list,
+                                             int* count, int* order, int* cost, int* diag, sr_dev_start* start,
+                                             hipEvent_t* ev4, hipStream_t stream) {
+    dim3 block(256);
+    dim3 grid((fr->width + 15) / 16, (fr->nrows + 15) / 16);
+    if (grid.x == 0 || grid.y == 0) return hipSuccess;
+    const unsigned nblocks = grid.x * grid.y;
+    const unsigned B = (unsigned)fr->batch;
+    if (B < 1 || B > SR_MAX_BATCH || fr->tiles != (int)nblocks) return hipErrorInvalidValue;
+    if ((size_t)nblocks * B * 256 > ps_n || (size_t)nblocks * B * 256 > (size_t)INT32_MAX) return hipErrorInvalidValue;
+    if ((cost == nullptr) != (order == nullptr) || fr->wave_cost) return hipErrorInvalidValue;
+    const int split = order ? fr->split_tiles : 0;
+    if (split < 0 || (split && (fr->split_log2 < 0 || fr->split_log2 > 4 || (fr->split_log2 & 1))))
+        return hipErrorInvalidValue;
+    if (nblocks > (1u << 22)) return hipErrorInvalidValue;  // tile << 8 stays a positive int
+    if (fr->projection < SR_PROJECTION_RECTILINEAR || fr->projection > SR_PROJECTION_FISHEYE) return hipErrorInvalidValue;
+    const unsigned slots = nblocks + ((64u >> (split ? fr->split_log2 : 6)) - 1u) * (unsigned)split;
+    const bool cull = fr->cull != 0;
+    const bool small = cull && fr->num_budget <= SR_NB_SMALL && fr->num_budget_cyl <= SR_NC_SMALL;
+    if (cull && fr->num_budget_cyl > SR_NC_KERNEL && !small) return hipErrorInvalidValue;
+    if (!sc || !xtab || !start) return hipErrorInvalidValue;
+    if (ev4) (void)hipEventRecord(ev4[0], stream);
+    hipLaunchKernelGGL(sr_start_table_seq_kernel, dim3(B), dim3(1), 0, stream, sc, segs, *fr, start, xtab);
+    const dim3 igrid(slots * B * SR_WG_PER_TILE);
+    if (fr->projection == SR_PROJECTION_EQUIRECT)
+        launch_integrate_seq<SR_PROJECTION_EQUIRECT>(cull, small, igrid, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count,
+                                                     order, cost, start);
+    else if (fr->projection == SR_PROJECTION_FISHEYE)
+        launch_integrate_seq<SR_PROJECTION_FISHEYE>(cull, small, igrid, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count,
+                                                    order, cost, start);
+    else
+        launch_integrate_seq<SR_PROJECTION_RECTILINEAR>(cull, small, igrid, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n,
+                                                        count, order, cost, start);
+    if (ev4) (void)hipEventRecord(ev4[1], stream);
+    OrderArgs oa{cost, order, (int)nblocks, fr->max_steps, split, split ? fr->split_log2 : 6, fr->split_min_steps};
+    hipLaunchKernelGGL((sr_shade_kernel<false, true>), dim3(grid.x, grid.y * B + (order ? 1u : 0u)), block, 0, stream, sc, segs,
+                       bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa, (const int*)nullptr);
+    if (ev4) (void)hipEventRecord(ev4[2], stream);
+    {
+        const unsigned tiles = nblocks * B;
+        const dim3 rgrid((tiles < SR_RESUME_TILES ? tiles : SR_RESUME_TILES) * SR_WG_PER_TILE);
+        const auto go = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, rgrid, dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n, out, pitch,
+                               dbg_rgba, dbg_steps, list, count);
+        };
+        if (cull)
+            go(sr_resume_kernel<true, false, true>);
+        else
+            go(sr_resume_kernel<false, false, true>);
+    }
+    if (ev4) (void)hipEventRecord(ev4[3], stream);
     return hipGetLastError();
 }

@@ -21,6 +21,13 @@ hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* tbl, const f
                               size_t pitch, float* dbg_rgba, int32_t* dbg_steps, float* ps, size_t ps_n, int* list,
                               int* count, int* order, int* cost, int* diag, sr_dev_start* start, hipEvent_t* ev4,
                               hipStream_t stream);
+// the frames of a scene sequence (sr.h "Scene sequences"): frame f reads the scene sc[f]; xtab: the scenes'
+// low-energy exclusions, 2 * SR_MAX_BUDGET floats each (xlow_need, then xperi_e)
+hipError_t sr_launch_geodesic_seq(const sr_dev_scene* sc, const float* xtab, const float4* tbl, const float* segs,
+                                  const uint32_t* bg, const uint32_t* arr, const uint8_t* opq, const sr_dev_frame* fr,
+                                  uint8_t* out, size_t pitch, float* dbg_rgba, int32_t* dbg_steps, float* ps, size_t ps_n,
+                                  int* list, int* count, int* order, int* cost, int* diag, sr_dev_start* start,
+                                  hipEvent_t* ev4, hipStream_t stream);
 // the shade and resume kernels alone, on pixel state a launch left (sr_reshade)
 hipError_t sr_launch_reshade(const sr_dev_scene* sc, const float4* tbl, const float* segs, const uint32_t* bg,
                              const uint32_t* arr, const sr_dev_frame* fr, uint8_t* out, size_t pitch, float* dbg_rgba,

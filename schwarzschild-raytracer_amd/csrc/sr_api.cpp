@@ -143,6 +143,21 @@ struct sr_ctx {
     } kept;
     // the scene of the last successful sr_set_scene (sr_scene_shading_only's left side)
     sr_scene scene_src;
+    // the scene sequence (sr.h "Scene sequences"): its images as one device
+    // array and their host copies (sr_set_test_ray packs their test-ray part
+    // again); a state of its own beside d_scene / h_scene
+    sr_dev_scene* d_seq = nullptr;
+    std::vector<sr_dev_scene> h_seq;
+    // the sequence's low-energy exclusions per (u_f, step angle) (their bits):
+    // xlow_need, then xperi_e, of every scene, as sr_launch_geodesic_seq reads
+    // them. Frames in flight keep the table they were launched with: an entry
+    // goes in stream order (evict_lru) or, with the sequence, after a wait.
+    struct XTab {
+        float* dev = nullptr;
+        std::vector<float> host;  // source of the stream-ordered upload
+        uint64_t used = 0;
+    };
+    std::map<std::pair<uint32_t, uint32_t>, XTab> xtabs;
 };
 
 namespace {
@@ -194,6 +209,50 @@ int ensure_table(sr_ctx* ctx, int max_steps, int max_revs, hipStream_t s, const 
     }
     *out = t.dev;
     return SR_OK;
+}
+
+// Floats per scene of an exclusion table (geodesic.hip SR_XTAB_FLOATS)
+constexpr size_t kXTabFloats = 2 * SR_MAX_BUDGET;
+
+// The sequence's exclusion table for a launch's (u_f, step angle): computed
+// and uploaded once per pair on the caller's stream, like a step table.
+int ensure_xtab(sr_ctx* ctx, float u_f, float max_dphi, hipStream_t s, const float** out) {
+    uint32_t ku, kd;
+    std::memcpy(&ku, &u_f, sizeof ku);
+    std::memcpy(&kd, &max_dphi, sizeof kd);
+    const auto key = std::make_pair(ku, kd);
+    auto it = ctx->xtabs.find(key);
+    if (it != ctx->xtabs.end()) {
+        it->second.used = ++ctx->tick;
+        *out = it->second.dev;
+        return SR_OK;
+    }
+    evict_lru(ctx, ctx->xtabs, [&](sr_ctx::XTab& t) { release(ctx, t.dev, ctx->last_stream); });
+    sr_ctx::XTab& t = ctx->xtabs[key];
+    t.host.resize(ctx->h_seq.size() * kXTabFloats);
+    for (size_t k = 0; k < ctx->h_seq.size(); k++)
+        sr_pre::low_energy_exclusions(ctx->h_seq[k], u_f, max_dphi, &t.host[k * kXTabFloats],
+                                      &t.host[k * kXTabFloats + SR_MAX_BUDGET]);
+    t.used = ++ctx->tick;
+    const size_t bytes = t.host.size() * sizeof(float);
+    if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&t.dev), bytes, s))) {
+        ctx->xtabs.erase(key);
+        return SR_E_NOMEM;
+    }
+    if (!hip_ok(hipMemcpyAsync(t.dev, t.host.data(), bytes, hipMemcpyHostToDevice, s))) {
+        release(ctx, t.dev, s);
+        ctx->xtabs.erase(key);
+        return SR_E_HIP;
+    }
+    *out = t.dev;
+    return SR_OK;
+}
+
+// Drops every exclusion table (the sequence they were computed from goes);
+// the context's frames are done (wait_ctx), the frees are stream-ordered all the same
+void drop_xtabs(sr_ctx* ctx) {
+    for (auto& kv : ctx->xtabs) release(ctx, kv.second.dev, ctx->upload);
+    ctx->xtabs.clear();
 }
 
 // Synchronous upload of host bytes into a fresh device buffer on the
@@ -444,6 +503,9 @@ struct Launch {
     // height and the rows are the output frame's
     int grid = 1;
     const uint8_t* phases = nullptr;
+    // a sequence launch (sr.h "Scene sequences"; -1: none): frame f renders
+    // scene seq_first + f of the context's sequence, not its own scene
+    int seq_first = -1;
     sr_stream stream = nullptr;
 
     Launch() = default;
@@ -475,6 +537,10 @@ struct Launch {
         d_block_list = d_list;
         return *this;
     }
+    Launch& sequence(int first_scene) {
+        seq_first = first_scene < 0 ? INT32_MIN : first_scene;  // a negative index is rejected, not "none"
+        return *this;
+    }
     Launch& into(uint8_t* dev_out, size_t pitch_bytes, size_t frame_stride_bytes = 0) {
         out = dev_out;
         pitch = pitch_bytes;
@@ -484,10 +550,13 @@ struct Launch {
 };
 
 // A launch's rejections of the context and its frames, ahead of any allocation
-int check_frames(const sr_ctx* c, const sr_camera* cams, int n_frames, const sr_params* p, int width, int height) {
+// (seq_first: Launch::seq_first; a sequence launch needs the sequence, not sr_set_scene)
+int check_frames(const sr_ctx* c, const sr_camera* cams, int n_frames, const sr_params* p, int width, int height,
+                 int seq_first = -1) {
     if (!c) return SR_E_INVALID;
-    if (!c->scene_set) return SR_E_NOT_READY;
+    if (seq_first == -1 ? !c->scene_set : c->h_seq.empty()) return SR_E_NOT_READY;
     if (!cams || n_frames < 1) return SR_E_INVALID;
+    if (seq_first != -1 && (seq_first < 0 || (size_t)seq_first + (size_t)n_frames > c->h_seq.size())) return SR_E_INVALID;
     if (n_frames > SR_MAX_BATCH) return SR_E_CAPACITY;
     return sr_pre::check_frame_args(cams, p, width, height);
 }
@@ -496,8 +565,10 @@ int check_frames(const sr_ctx* c, const sr_camera* cams, int n_frames, const sr_
 // derive_frame, the low-energy exclusions per (u_f, step angle)), the
 // context's settings and the request's rows. No HIP call.
 int build_frame(sr_ctx* ctx, const Launch& r, sr_dev_frame& fr) {
-    const int rc = check_frames(ctx, r.cams, r.n_frames, r.params, r.width, r.height);
+    const int rc = check_frames(ctx, r.cams, r.n_frames, r.params, r.width, r.height, r.seq_first);
     if (rc != SR_OK) return rc;
+    const bool seq = r.seq_first != -1;
+    if (seq && (r.phases || r.d_codes || r.d_wave_cost)) return SR_E_INVALID;
     if (r.phases) {
         if (r.grid < 1 || r.grid > SR_MAX_SUPERSAMPLE || r.width > INT32_MAX / (2 * r.grid) ||
             r.height > INT32_MAX / (2 * r.grid))
@@ -511,14 +582,26 @@ int build_frame(sr_ctx* ctx, const Launch& r, sr_dev_frame& fr) {
     if (r.n_frames > 1 && (!r.out || r.frame_stride < r.pitch * (size_t)r.nrows || r.dbg_rgba || r.dbg_steps))
         return SR_E_INVALID;
     sr_pre::derive_frame({r.cams, r.n_frames, r.params, r.width, r.height, r.grid, r.phases, ctx->cull, ctx->projection},
-                         ctx->h_scene, fr);
-    if (!(ctx->xc_uf == fr.u_f && ctx->xc_dphi == fr.max_dphi)) {
-        sr_pre::low_energy_exclusions(ctx->h_scene, fr.u_f, fr.max_dphi, ctx->xc_need, ctx->xc_peri);
-        ctx->xc_uf = fr.u_f;
-        ctx->xc_dphi = fr.max_dphi;
+                         seq ? ctx->h_seq[(size_t)r.seq_first] : ctx->h_scene, fr);
+    if (seq) {
+        // the slot counts pick the integrate kernel's capacity: the window's
+        // maxima. The exclusions stay derive_frame's "none": each frame's
+        // own are in its start record (ensure_xtab).
+        for (int f = 1; f < r.n_frames; f++) {
+            const sr_dev_scene& sc = ctx->h_seq[(size_t)(r.seq_first + f)];
+            const int cyl = __builtin_popcount((unsigned)sc.budget_cyl_mask);
+            if (sc.num_budget > fr.num_budget) fr.num_budget = sc.num_budget;
+            if (cyl > fr.num_budget_cyl) fr.num_budget_cyl = cyl;
+        }
+    } else {
+        if (!(ctx->xc_uf == fr.u_f && ctx->xc_dphi == fr.max_dphi)) {
+            sr_pre::low_energy_exclusions(ctx->h_scene, fr.u_f, fr.max_dphi, ctx->xc_need, ctx->xc_peri);
+            ctx->xc_uf = fr.u_f;
+            ctx->xc_dphi = fr.max_dphi;
+        }
+        std::memcpy(fr.xlow_need, ctx->xc_need, sizeof fr.xlow_need);
+        std::memcpy(fr.xperi_e, ctx->xc_peri, sizeof fr.xperi_e);
     }
-    std::memcpy(fr.xlow_need, ctx->xc_need, sizeof fr.xlow_need);
-    std::memcpy(fr.xperi_e, ctx->xc_peri, sizeof fr.xperi_e);
     fr.bg_w = ctx->bg_w;
     fr.bg_h = ctx->bg_h;
     fr.arr_w = ctx->arr_w;
@@ -563,15 +646,27 @@ int launch(sr_ctx* ctx, const Launch& r) {
         ctx->last_order = order;
         ctx->last_slots = launch_slots(ctx, (size_t)gx * (size_t)gy);
     }
-    const hipError_t e = sr_launch_geodesic(
-        ctx->d_scene, tbl, ctx->d_segs, ctx->d_bg, ctx->d_arr, ctx->d_opq, &fr, r.out, r.pitch, r.dbg_rgba, r.dbg_steps,
-        ctx->d_ps, ctx->ps_n, ctx->d_list, ctx->d_count, order, cost, ctx->d_diag, ctx->d_start,
-        ctx->timing_n < ctx->timing_cap ? &ctx->tev[4 * (size_t)ctx->timing_n++] : nullptr, s);
+    const bool seq = r.seq_first != -1;
+    const float* xtab = nullptr;
+    if (seq) {
+        rc = ensure_xtab(ctx, fr.u_f, fr.max_dphi, s, &xtab);
+        if (rc != SR_OK) return rc;
+    }
+    hipEvent_t* const ev4 = ctx->timing_n < ctx->timing_cap ? &ctx->tev[4 * (size_t)ctx->timing_n++] : nullptr;
+    const hipError_t e =
+        seq ? sr_launch_geodesic_seq(ctx->d_seq + r.seq_first, xtab + (size_t)r.seq_first * kXTabFloats, tbl, ctx->d_segs,
+                                     ctx->d_bg, ctx->d_arr, ctx->d_opq, &fr, r.out, r.pitch, r.dbg_rgba, r.dbg_steps,
+                                     ctx->d_ps, ctx->ps_n, ctx->d_list, ctx->d_count, order, cost, ctx->d_diag,
+                                     ctx->d_start, ev4, s)
+            : sr_launch_geodesic(ctx->d_scene, tbl, ctx->d_segs, ctx->d_bg, ctx->d_arr, ctx->d_opq, &fr, r.out, r.pitch,
+                                 r.dbg_rgba, r.dbg_steps, ctx->d_ps, ctx->ps_n, ctx->d_list, ctx->d_count, order, cost,
+                                 ctx->d_diag, ctx->d_start, ev4, s);
     rc = finish(ctx, e, s);
     // the retained frame: whole launches of at least one row (a sparse launch
     // holds only its tiles' rays, sr_wave_costs writes no pixels; the callers
-    // that launch more after this one, launch_ss and the rest, amend or drop it)
-    if (rc == SR_OK && r.nrows > 0 && !r.d_codes && !r.d_wave_cost) {
+    // that launch more after this one, launch_ss and the rest, amend or drop
+    // it). None after a sequence launch: "the current scene" has no meaning for it.
+    if (rc == SR_OK && r.nrows > 0 && !r.d_codes && !r.d_wave_cost && !seq) {
         ctx->kept.fr = fr;
         ctx->kept.max_steps = r.params->max_steps;
         ctx->kept.max_revolutions = r.params->max_revolutions;
@@ -785,6 +880,8 @@ void sr_destroy(sr_ctx* c) {
         release(c, c->d_arr, s);
         release(c, c->d_opq, s);
         for (auto& kv : c->tables) release(c, kv.second.dev, s);
+        for (auto& kv : c->xtabs) release(c, kv.second.dev, s);
+        release(c, c->d_seq, s);
         free_pixel_state(c, s);
         release(c, c->d_ss, s);
         release(c, c->d_amask, s);
@@ -881,8 +978,48 @@ int sr_set_test_ray(sr_ctx* c, const sr_test_ray* t) {
         !hip_ok(hipStreamSynchronize(c->upload)))
         return SR_E_HIP;
     c->h_scene = d;
+    // the sequence's scenes carry the test-ray part too (it passed above:
+    // pack_test_ray rejects ahead of any write, and not by the scene part)
+    if (!c->h_seq.empty()) {
+        for (sr_dev_scene& q : c->h_seq) (void)sr_pre::pack_test_ray(*t, q, segs);
+        if (!hip_ok(hipMemcpyAsync(c->d_seq, c->h_seq.data(), c->h_seq.size() * sizeof(sr_dev_scene),
+                                   hipMemcpyHostToDevice, c->upload)) ||
+            !hip_ok(hipStreamSynchronize(c->upload)))
+            return SR_E_HIP;
+    }
     return SR_OK;
 }
+
+// ---- scene sequences (sr.h): the scenes of an animation as one device
+// array; a launch renders frame f from scene first_scene + f (Launch::sequence)
+
+int sr_set_scene_sequence(sr_ctx* c, const sr_scene* scenes, int n) {
+    if (!c || n < 0 || (n > 0 && !scenes)) return SR_E_INVALID;
+    if (n > SR_MAX_SEQUENCE) return SR_E_CAPACITY;
+    std::vector<sr_dev_scene> seq((size_t)n, c->h_scene);  // the context's test-ray part (sr_set_scene's own start)
+    for (int k = 0; k < n; k++) {
+        const int rc = sr_pre::pack_scene(scenes[k], seq[(size_t)k]);
+        if (rc != SR_OK) return rc;  // the earlier sequence stays
+    }
+    if (!hip_ok(hipSetDevice(c->device)) || !wait_ctx(c)) return SR_E_HIP;
+    drop_xtabs(c);
+    c->h_seq.clear();
+    if (n == 0) {
+        release(c, c->d_seq, c->upload);
+        c->d_seq = nullptr;
+        return SR_OK;
+    }
+    const int rc = upload_bytes(c, seq.data(), seq.size() * sizeof(sr_dev_scene), reinterpret_cast<void**>(&c->d_seq));
+    if (rc != SR_OK) {
+        release(c, c->d_seq, c->upload);
+        c->d_seq = nullptr;
+        return rc;
+    }
+    c->h_seq = std::move(seq);
+    return SR_OK;
+}
+
+int sr_scene_sequence_length(sr_ctx* c) { return c ? (int)c->h_seq.size() : SR_E_INVALID; }
 
 int sr_render(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int row_begin,
               int row_end, uint8_t* out, size_t pitch, sr_stream stream) {
@@ -940,6 +1077,64 @@ int sr_render_blocks_batch(sr_ctx* c, const sr_camera* cams, int n_frames, const
     return launch(c, Launch(cams, n_frames, p, width, height, stream)
                          .strided_blocks(block_rows, block_first, block_step)
                          .into(out, pitch, frame_stride));
+}
+
+static bool bad_grid(int ss);
+
+int sr_render_sequence(sr_ctx* c, int first_scene, const sr_camera* cams, int n_frames, const sr_params* p, int width,
+                       int height, int row_begin, int row_end, int ss, uint8_t* out, size_t pitch,
+                       size_t frame_stride, sr_stream stream) {
+    if (bad_grid(ss)) return SR_E_INVALID;
+    if (!out || bad_rows(row_begin, row_end, height)) return SR_E_INVALID;
+    const int n = row_end - row_begin;
+    const Launch r = Launch(cams, n_frames, p, width, height, stream)
+                         .band(row_begin, n)
+                         .sequence(first_scene)
+                         .into(out, pitch, frame_stride);
+    if (ss == 1) return launch(c, r);
+    int rc = check_frames(c, cams, n_frames, p, width, height, r.seq_first);
+    if (rc != SR_OK) return rc;
+    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss || n > (1 << 24) / ss)
+        return SR_E_INVALID;
+    if (n_frames > 1 && frame_stride < pitch * (size_t)n) return SR_E_INVALID;
+    if (n == 0) {  // no rows: nothing is written
+        c->kept.valid = false;
+        return SR_OK;
+    }
+    return launch_ss(c, r, ss);
+}
+
+int sr_render_sequence_block_list(sr_ctx* c, int first_scene, const sr_camera* cams, int n_frames, const sr_params* p,
+                                  int width, int height, int block_rows, const int* blocks, int n_blocks, int ss,
+                                  uint8_t* out, size_t pitch, size_t frame_stride, sr_stream stream) {
+    if (bad_grid(ss)) return SR_E_INVALID;
+    int rc = check_block_list(c, out, blocks, n_blocks, block_rows, height, ss);
+    if (rc == SR_OK) rc = check_frames(c, cams, n_frames, p, width, height, first_scene < 0 ? INT32_MIN : first_scene);
+    if (rc != SR_OK) return rc;
+    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss) return SR_E_INVALID;
+    if (n_frames > 1 && frame_stride < pitch * (size_t)(n_blocks * block_rows)) return SR_E_INVALID;
+    const int* d = nullptr;
+    rc = ensure_block_list(c, blocks, n_blocks, stream, &d);
+    if (rc != SR_OK) return rc;
+    const Launch r = Launch(cams, n_frames, p, width, height, stream)
+                         .block_list(d, n_blocks, block_rows)
+                         .sequence(first_scene)
+                         .into(out, pitch, frame_stride);
+    return ss == 1 ? launch(c, r) : launch_ss(c, r, ss);
+}
+
+int sr_render_sequence_debug(sr_ctx* c, int scene_index, const sr_camera* cam, const sr_params* p, int width,
+                             int height, int row_begin, int row_end, float* dbg_rgba, uint8_t* out,
+                             int32_t* dbg_steps, sr_stream stream) {
+    if (bad_rows(row_begin, row_end, height)) return SR_E_INVALID;
+    if (!dbg_rgba && !out && !dbg_steps) return SR_E_INVALID;
+    Launch r = Launch(cam, 1, p, width, height, stream)
+                   .band(row_begin, row_end - row_begin)
+                   .sequence(scene_index)
+                   .into(out, (size_t)width * 4);
+    r.dbg_rgba = dbg_rgba;
+    r.dbg_steps = dbg_steps;
+    return launch(c, r);
 }
 
 int sr_resolve_box(const uint8_t* samples, size_t sample_pitch, size_t sample_frame_stride, int width, int rows, int ss,

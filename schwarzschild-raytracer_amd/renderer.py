@@ -381,6 +381,76 @@ class Renderer:
         )
         return f, b, s
 
+    # ---- scene sequences (sr.h): one launch renders frames of different scenes ----
+    def set_scene_sequence(self, scenes) -> None:
+        """sr_set_scene_sequence: snapshot copies of the scenes (at most
+        abi.MAX_SEQUENCE) as the context's sequence; an empty list clears it."""
+        scenes = list(scenes)
+        arr = (abi.Scene * max(1, len(scenes)))(*scenes)
+        abi.check(self.lib.sr_set_scene_sequence(self.ctx, arr, len(scenes)), "sr_set_scene_sequence")
+
+    def scene_sequence_length(self) -> int:
+        return int(self.lib.sr_scene_sequence_length(self.ctx))
+
+    def render_sequence(self, first_scene: int, cams, params: abi.Params, width: int, height: int, row_begin: int = 0,
+                        row_end: int | None = None, ss: int = 1, out=None, stream=None):
+        """sr_render_sequence: rows [row_begin, row_end) of len(cams) frames in
+        one launch, frame f of scene first_scene + f of the sequence with
+        cams[f] -> [B, rows, W, 4]. Asynchronous."""
+        row_end = height if row_end is None else row_end
+        rows = max(row_end - row_begin, 0)
+        B = len(cams)
+        arr = (abi.Camera * B)(*cams)
+        if out is None:
+            out = self.torch.empty((B, rows, width, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and tuple(out.shape[:1]) == (B,)
+        assert out[0].numel() >= rows * width * 4
+        abi.check(
+            self.lib.sr_render_sequence(self.ctx, int(first_scene), arr, B, C.byref(params), width, height, row_begin,
+                                        row_end, int(ss), C.c_void_p(out.data_ptr()), width * 4, out[0].numel(),
+                                        self._stream(stream)),
+            "sr_render_sequence",
+        )
+        return out
+
+    def render_sequence_block_list(self, first_scene: int, cams, params: abi.Params, width: int, height: int,
+                                   block_rows: int, blocks, ss: int = 1, out=None, stream=None):
+        """render_sequence for the rows of an explicit block list (-1 = padding)
+        -> [B, len(blocks) * block_rows, W, 4]."""
+        blocks = [int(b) for b in blocks]
+        B = len(cams)
+        arr = (abi.Camera * B)(*cams)
+        lst = (C.c_int * len(blocks))(*blocks)
+        rows = len(blocks) * block_rows
+        if out is None:
+            out = self.torch.empty((B, rows, width, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and tuple(out.shape[:1]) == (B,)
+        assert out[0].numel() >= rows * width * 4
+        abi.check(
+            self.lib.sr_render_sequence_block_list(self.ctx, int(first_scene), arr, B, C.byref(params), width, height,
+                                                   block_rows, lst, len(blocks), int(ss), C.c_void_p(out.data_ptr()),
+                                                   width * 4, out[0].numel(), self._stream(stream)),
+            "sr_render_sequence_block_list",
+        )
+        return out
+
+    def render_sequence_debug(self, scene_index: int, cam: abi.Camera, params: abi.Params, width: int, height: int,
+                              row_begin: int = 0, row_end: int | None = None, stream=None):
+        """render_debug of scene scene_index of the sequence."""
+        t = self.torch
+        row_end = height if row_end is None else row_end
+        rows = row_end - row_begin
+        f = t.empty((rows, width, 4), dtype=t.float32, device=self.tdev)
+        b = t.empty((rows, width, 4), dtype=t.uint8, device=self.tdev)
+        s = t.empty((rows, width), dtype=t.int32, device=self.tdev)
+        abi.check(
+            self.lib.sr_render_sequence_debug(self.ctx, int(scene_index), C.byref(cam), C.byref(params), width, height,
+                                              row_begin, row_end, C.c_void_p(f.data_ptr()), C.c_void_p(b.data_ptr()),
+                                              C.c_void_p(s.data_ptr()), self._stream(stream)),
+            "sr_render_sequence_debug",
+        )
+        return f, b, s
+
     # ---- retained frames (sr.h): relight and pick from the last launch's rays ----
     def can_reshade(self) -> bool:
         """sr_can_reshade: the context holds a retained frame reshade() would accept."""

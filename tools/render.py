@@ -14,8 +14,12 @@ hyperbolic trajectory (src/main.cpp:404-410) in batched launches.
   python tools/render.py --projection equirect --fov 360 --width 2048 --height 1024 --out pano.png
   python tools/render.py --projection fisheye --fov 180 --width 1080 --height 1080 --out dome.png
                                   (sr_set_projection: a 360 degree panorama, a dome master)
+  python tools/render.py --orbit-frames 48 --out orbit_%02d.png
+                                  (the default scene's sphere on a circular orbit: the scenes as one
+                                   sequence, sr_set_scene_sequence, rendered 32 frames per launch)
 """
 import argparse
+import math
 import sys
 from pathlib import Path
 
@@ -53,7 +57,14 @@ def main():
     ap.add_argument("--fov", type=float, default=None,
                     help="the camera's field of view in degrees (default: the app's); under equirect and fisheye "
                          "the angle the frame's width spans, up to 360")
+    ap.add_argument("--orbit-frames", type=int, default=0, metavar="N",
+                    help="N frames (1 .. 256) of the default scene with its sphere on a circular orbit of its own radius "
+                         "about the hole, rendered through one scene sequence (sr_render_sequence; --out with %%d)")
     args = ap.parse_args()
+    if args.orbit_frames and (args.flyby > 0 or args.adaptive is not None or args.progressive is not None):
+        ap.error("--orbit-frames is a mode of its own: no --flyby, --adaptive or --progressive")
+    if not 0 <= args.orbit_frames <= 256:
+        ap.error("--orbit-frames takes 1 .. 256 frames (SR_MAX_SEQUENCE)")
     if args.progressive is not None and (args.ssaa != 1 or args.adaptive is not None or args.flyby > 0):
         ap.error("--progressive takes the grid itself: no --ssaa, --adaptive or --flyby")
     if args.adaptive is not None and (args.ssaa < 2 or args.flyby > 0):
@@ -85,7 +96,27 @@ def main():
             cam.fov = args.fov
         return cam
 
-    if args.progressive is not None:
+    if args.orbit_frames:
+        n = args.orbit_frames
+        scenes = []
+        for k in range(n):  # the sphere once around the hole, in the plane and at the distance it starts at
+            s = sc.scene_default(textured=True)
+            pos = s.spheres[0].transform.pos
+            radius, phase = math.hypot(pos[0], pos[2]), math.atan2(pos[2], pos[0])
+            pos[0] = radius * math.cos(phase + 2.0 * math.pi * k / n)
+            pos[2] = radius * math.sin(phase + 2.0 * math.pi * k / n)
+            scenes.append(s)
+        r.set_scene_sequence(scenes)
+        per = max(1, min(32, (2 << 30) // (4 * args.ssaa ** 2 * W * H)))
+        for first in range(0, n, per):
+            m = min(per, n - first)
+            out = r.render_sequence(first, [camera()] * m, params, W, H, ss=args.ssaa)
+            torch.cuda.synchronize()
+            for k, fr in enumerate(out.cpu().numpy()):
+                path = args.out % (first + k) if "%" in args.out else f"{Path(args.out).stem}_{first + k:03d}.png"
+                abi.write_png(path, fr)
+                print(f"wrote {path}")
+    elif args.progressive is not None:
         for k, frame in r.progressive(camera(), params, W, H, args.progressive):
             torch.cuda.synchronize()
             path = args.out % k if "%" in args.out else f"{Path(args.out).stem}_{k:02d}.png"
