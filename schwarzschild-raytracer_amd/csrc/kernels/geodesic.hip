@@ -108,6 +108,7 @@ struct Tex {
 };
 
 #include "probes.h"
+#include "uniform.h"
 
 // ---- primitive tests: return the reference's is_hit and fill p ------------
 // sphere_intersect, frag:457-478 (r2: the float square r * r of the radius):
@@ -579,35 +580,35 @@ __device__ __forceinline__ bool outward_slot(const sr_dev_slot& sl, bool cyl_par
 
 // A budget slot's record read in one batch of scalar loads: every field is
 // pinned to an SGPR where it is loaded, so the type-specific code that
-// follows does not wait on a chain of lazily issued loads.
-#define SR_PIN(x) asm volatile("" : "+s"(x))
+// follows does not wait on a chain of lazily issued loads. (SR_PIN: uniform.h;
+// its first argument names the site for the SR_CHECK_UNIFORM build)
 __device__ __forceinline__ sr_dev_slot pin_slot(const sr_dev_slot& g) {
     sr_dev_slot sl = g;
-    SR_PIN(sl.type);
-    SR_PIN(sl.rb);
-    SR_PIN(sl.mp);
-    SR_PIN(sl.br);
-    SR_PIN(sl.mu);
-    SR_PIN(sl.pl1);
-    SR_PIN(sl.qk);
-    SR_PIN(sl.bc[0]);
-    SR_PIN(sl.bc[1]);
-    SR_PIN(sl.bc[2]);
-    SR_PIN(sl.x0);
-    SR_PIN(sl.pos[0]);
-    SR_PIN(sl.pos[1]);
-    SR_PIN(sl.pos[2]);
-    SR_PIN(sl.x1);
-    SR_PIN(sl.a0[0]);
-    SR_PIN(sl.a0[1]);
-    SR_PIN(sl.a0[2]);
-    SR_PIN(sl.x2);
-    SR_PIN(sl.a1[0]);
-    SR_PIN(sl.a1[1]);
-    SR_PIN(sl.a1[2]);
-    SR_PIN(sl.a2[0]);
-    SR_PIN(sl.a2[1]);
-    SR_PIN(sl.a2[2]);
+    SR_PIN(SLOT_TYPE, sl.type);
+    SR_PIN(SLOT_RB, sl.rb);
+    SR_PIN(SLOT_MP, sl.mp);
+    SR_PIN(SLOT_BR, sl.br);
+    SR_PIN(SLOT_MU, sl.mu);
+    SR_PIN(SLOT_PL1, sl.pl1);
+    SR_PIN(SLOT_QK, sl.qk);
+    SR_PIN(SLOT_BC0, sl.bc[0]);
+    SR_PIN(SLOT_BC1, sl.bc[1]);
+    SR_PIN(SLOT_BC2, sl.bc[2]);
+    SR_PIN(SLOT_X0, sl.x0);
+    SR_PIN(SLOT_POS0, sl.pos[0]);
+    SR_PIN(SLOT_POS1, sl.pos[1]);
+    SR_PIN(SLOT_POS2, sl.pos[2]);
+    SR_PIN(SLOT_X1, sl.x1);
+    SR_PIN(SLOT_A00, sl.a0[0]);
+    SR_PIN(SLOT_A01, sl.a0[1]);
+    SR_PIN(SLOT_A02, sl.a0[2]);
+    SR_PIN(SLOT_X2, sl.x2);
+    SR_PIN(SLOT_A10, sl.a1[0]);
+    SR_PIN(SLOT_A11, sl.a1[1]);
+    SR_PIN(SLOT_A12, sl.a1[2]);
+    SR_PIN(SLOT_A20, sl.a2[0]);
+    SR_PIN(SLOT_A21, sl.a2[1]);
+    SR_PIN(SLOT_A22, sl.a2[2]);
     return sl;
 }
 
@@ -1174,18 +1175,18 @@ __device__ void build_start(const sr_dev_scene* __restrict__ sc, const float* __
 // A start slot's record in one batch of scalar loads (as pin_slot)
 __device__ __forceinline__ sr_dev_start_slot pin_start_slot(const sr_dev_start_slot& g) {
     sr_dev_start_slot t = g;
-    SR_PIN(t.e);
-    SR_PIN(t.k2r);
-    SR_PIN(t.need);
-    SR_PIN(t.flags);
-    SR_PIN(t.bc[0]);
-    SR_PIN(t.bc[1]);
-    SR_PIN(t.bc[2]);
-    SR_PIN(t.xneed);
-    SR_PIN(t.wn[0]);
-    SR_PIN(t.wn[1]);
-    SR_PIN(t.wn[2]);
-    SR_PIN(t.xperi);
+    SR_PIN(START_E, t.e);
+    SR_PIN(START_K2R, t.k2r);
+    SR_PIN(START_NEED, t.need);
+    SR_PIN(START_FLAGS, t.flags);
+    SR_PIN(START_BC0, t.bc[0]);
+    SR_PIN(START_BC1, t.bc[1]);
+    SR_PIN(START_BC2, t.bc[2]);
+    SR_PIN(START_XNEED, t.xneed);
+    SR_PIN(START_WN0, t.wn[0]);
+    SR_PIN(START_WN1, t.wn[1]);
+    SR_PIN(START_WN2, t.wn[2]);
+    SR_PIN(START_XPERI, t.xperi);
     return t;
 }
 
@@ -1214,14 +1215,14 @@ __device__ __forceinline__ void budget_start(const sr_dev_scene* __restrict__ sc
     float e0 = st.e_bh[0], e1 = st.e_bh[1], uh0 = st.uhi[0], uh1 = st.uhi[1];
     float kap = st.kap, a2s = st.a2s, cap = st.cap;
     int bh_out = st.bh_out;
-    SR_PIN(e0);
-    SR_PIN(e1);
-    SR_PIN(uh0);
-    SR_PIN(uh1);
-    SR_PIN(kap);
-    SR_PIN(a2s);
-    SR_PIN(cap);
-    SR_PIN(bh_out);
+    SR_PIN(HEAD_E0, e0);
+    SR_PIN(HEAD_E1, e1);
+    SR_PIN(HEAD_UH0, uh0);
+    SR_PIN(HEAD_UH1, uh1);
+    SR_PIN(HEAD_KAP, kap);
+    SR_PIN(HEAD_A2S, a2s);
+    SR_PIN(HEAD_CAP, cap);
+    SR_PIN(HEAD_BH_OUT, bh_out);
     {
         float e = falling ? e1 : e0;
         bs.setUhi(falling ? uh1 : uh0);
@@ -1231,8 +1232,8 @@ __device__ __forceinline__ void budget_start(const sr_dev_scene* __restrict__ sc
     }
     if constexpr (BS::TR) {
         float t0 = st.e_tr[0], t1 = st.e_tr[1];
-        SR_PIN(t0);
-        SR_PIN(t1);
+        SR_PIN(HEAD_TR0, t0);
+        SR_PIN(HEAD_TR1, t1);
         const float e = outward ? t1 : t0;
         bs.setEtr(e);
         m = nmin(m, e);
@@ -1489,7 +1490,7 @@ __device__ __forceinline__ uint32_t budget_event(const sr_dev_scene* __restrict_
     spent &= (2u << nb) - 1u;
     // uniform by construction (ballots); said so, so that the slot records
     // below stay scalar loads in every build (pin_slot's SGPR constraints)
-    spent = __builtin_amdgcn_readfirstlane(spent);
+    spent = SR_RFL(EVENT_SPENT, spent);
     SR_PTB(20);
     SR_PROBE(probe_event_phase1(bs, T, e[0], forced, spent));
     // the others run on: charge them the path since the last event
@@ -2094,8 +2095,8 @@ __device__ __forceinline__ m3 surface_frame(const sr_dev_obj& ob, const Hit& h, 
 // wave-uniform values so the object record is fetched with scalar loads.
 __device__ __forceinline__ f4 shade_hit(const sr_dev_scene* __restrict__ sc, const sr_dev_frame& fr, const Tex& tx,
                         Hit h, f3 view_dir) {
-    h.slot = __builtin_amdgcn_readfirstlane(h.slot);
-    h.face = __builtin_amdgcn_readfirstlane(h.face);
+    h.slot = SR_RFL(SHADE_SLOT, h.slot);
+    h.face = SR_RFL(SHADE_FACE, h.face);
     if (h.slot == SLOT_BH) return F4(0.0f, 0.0f, 0.0f, 1.0f);
     if (h.slot == SLOT_TR_CURVED)
         return F4(sc->tr_curved_color[0], sc->tr_curved_color[1], sc->tr_curved_color[2], sc->tr_curved_color[3]);
@@ -2240,7 +2241,7 @@ __device__ __forceinline__ int hit_opacity_uniform(const sr_dev_scene* __restric
     float tsx = sc->texture_sizes[ti][0], tsy = sc->texture_sizes[ti][1];
     float msx = sc->max_texture_size[0], msy = sc->max_texture_size[1];
     int aw = fr.arr_w, ah = fr.arr_h;
-    asm volatile("" : "+s"(tsx), "+s"(tsy), "+s"(msx), "+s"(msy), "+s"(aw), "+s"(ah));
+    SR_PIN6(OPQ_TSX, tsx, OPQ_TSY, tsy, OPQ_MSX, msx, OPQ_MSY, msy, OPQ_AW, aw, OPQ_AH, ah);
     f2 r = F2((uv.x * tsx) / msx, (uv.y * tsy) / msy);
     int layer = m.texture_index;
     if (layer > fr.arr_layers - 1) layer = fr.arr_layers - 1;
@@ -2260,8 +2261,8 @@ __device__ __forceinline__ int hit_opacity(const sr_dev_scene* __restrict__ sc, 
     for (;;) {  // waterfall: object data as wave-uniform loads
         const int first = __builtin_amdgcn_readfirstlane(key);
         if (key == first) {
-            op = hit_opacity_uniform(sc, fr, tx, __builtin_amdgcn_readfirstlane(hit.slot),
-                                     __builtin_amdgcn_readfirstlane(hit.face), hit, view_dir, zero_only);
+            op = hit_opacity_uniform(sc, fr, tx, SR_RFL(OPQ_SLOT, hit.slot), SR_RFL(OPQ_FACE, hit.face), hit, view_dir,
+                                     zero_only);
             break;
         }
     }
@@ -2719,7 +2720,7 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
     int i = r.i;
     SR_PROBE(LoopProbe lp(i); SR_PROF_LOOP_START(r, bs, prof_bi_));
     for (;;) {
-        if (RECORD) i = __builtin_amdgcn_readfirstlane(i);  // every lane started at step 0: keep i scalar
+        if (RECORD) i = SR_RFL(STEP_I, i);  // every lane started at step 0: keep i scalar
         // (sr_resume_kernel's lanes are unrelated rays at their own steps)
         if (i >= N) break;
         // the top of step i (the fast loop below leaves a step early whenever
@@ -2837,6 +2838,11 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
             // step would rotate. A use on each exit path keeps the loads where
             // they are issued (sunk to their first use, they would be waited
             // at once).
+            // A recording launch's entries are scalar loads (i is
+            // wave-uniform) and the use says so; sr_resume_kernel's lanes are at
+            // their own steps, their entries per-lane loads, and the use is a
+            // vector one (an "s" use there made the compiler read the first
+            // lane's value back for nothing: tests/test_gpu_uniformity.py).
             for (;;) {
                 float4 nx[FU];
 #pragma unroll
@@ -2847,7 +2853,10 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
                 for (int k = 0; k < FU && !leave; k++) {
                     if (compute(k)) {
 #pragma unroll
-                        for (int j = k; j < FU; j++) asm volatile("; keep %0" ::"s"(nx[j].x));
+                        for (int j = k; j < FU; j++) {
+                            if constexpr (RECORD) SR_KEEP(FAST_KEEP, nx[j].x);
+                            else SR_KEEP_LANE(nx[j].x);
+                        }
                         leave = true;
                     } else {
                         leave = apply(nx[k]);
@@ -2910,7 +2919,10 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
                         SR_STAT(13, __popcll(__ballot(1)));
                         if (__ballot(!(un >= lo && un <= hi))) {  // NaN leaves too
 #pragma unroll
-                            for (int j = k; j < FU; j++) asm volatile("; keep %0" ::"s"(nx[j].x));
+                            for (int j = k; j < FU; j++) {
+                                if constexpr (RECORD) SR_KEEP(COAST_KEEP, nx[j].x);
+                                else SR_KEEP_LANE(nx[j].x);
+                            }
                             leave = true;
                         } else {
                             r.u = un;
@@ -3656,7 +3668,7 @@ __global__ __launch_bounds__(SR_WG) void sr_resume_kernel(const sr_dev_scene* __
         for (int fu = 0; fu < (SEQ ? fr.batch : 1); fu++) {
             if constexpr (SEQ) {
                 if (f != fu) continue;
-                sc = scenes + __builtin_amdgcn_readfirstlane(f);
+                sc = scenes + SR_RFL(RESUME_FRAME, f);
             }
             for (;;) {  // rounds: integrate to the next hit, shade, resume if not opaque
                 Hit hit = no_hit();
