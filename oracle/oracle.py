@@ -60,8 +60,32 @@ def load() -> C.CDLL:
                                            C.POINTER(C.c_float)]
         lib.sro_pressr_ray_repeat.restype = C.c_int
         lib.sro_pressr_ray_repeat.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int]
+        lib.sro_intersect.restype = C.c_int
+        lib.sro_intersect.argtypes = [C.POINTER(abi.Scene), C.POINTER(abi.TestRay), C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
+
+
+# sro_intersect's winners that are not indices into scene.objects[]
+HIT_NONE, HIT_HOLE, HIT_TEST_RAY_FLAT, HIT_TEST_RAY_CURVED = -100, -1, -2, -3
+
+
+def intersect(scene, chords, test_ray=None):
+    """intersect()'s closest hit for float32 chords [n, 7] {origin, direction,
+    max_lambda (< 0: unbounded)} -> (winner [n] int32: the index in
+    scene.objects[] or a HIT_* code, part [n] int32: the box face or curved
+    segment, point [n, 3] float32, dist [n] float32). test_ray None: none visible."""
+    a = np.ascontiguousarray(chords, dtype=np.float32)
+    assert a.ndim == 2 and a.shape[1] == 7, a.shape
+    n = a.shape[0]
+    winner, part = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    pd = np.zeros((n, 4), dtype=np.float32)
+    rc = load().sro_intersect(C.byref(scene), C.byref(test_ray) if test_ray is not None else None, a.ctypes.data, n,
+                              winner.ctypes.data, part.ctypes.data, pd.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"sro_intersect failed: {rc}")
+    return winner, part, pd[:, :3].copy(), pd[:, 3].copy()
 
 
 # filter_mode of the oracle only: SwiftShader 4.1's fixed-point sampler (test infrastructure)

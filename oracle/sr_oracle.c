@@ -88,6 +88,7 @@ typedef struct {
     m3 tangent_space;
     v2 tangent_coordinates;
     Object object;
+    int part; /* sro_intersect only: the box face, or the curved test-ray segment */
 } HitInfo;
 
 enum {
@@ -573,6 +574,7 @@ static HitInfo box_intersect(Ray ray, const Box* b, float max_lambda) {
         }
     }
     if (!res.is_hit) return res;
+    res.part = closest_index;
     rectangle_tangent_space(&res, &rects[closest_index]);
     static const float off[6][2] = {{1, 0}, {1, 2}, {1, 1}, {3, 1}, {0, 1}, {2, 1}};
     if (off[closest_index][0] != 0.0f) res.tangent_coordinates.x += off[closest_index][0];
@@ -665,11 +667,13 @@ static m3 gram_schmidt(m3 m) {
 }
 static m3 test_ray_frame(v3 d) { return gram_schmidt(M3(V3(d.x, d.z, d.y), d, V3(d.z, d.x, d.y))); }
 
-/* frag:755-822 */
-static v4 intersect(const Ctx* c, Ray ray, float max_lambda) {
+/* frag:755-814: the closest hit; *object_at = its index in scene.objects[]
+ * (-1: the black hole or a test-ray cylinder, see object.type) */
+static HitInfo intersect_closest(const Ctx* c, Ray ray, float max_lambda, int* object_at) {
     static const Sphere BLACK_HOLE = {{{0, 0, 0}, {{{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}}}, 1.0f};
     HitInfo closest = sphere_intersect(ray, &BLACK_HOLE, max_lambda);
     closest.object.type = OBJECT_TYPE_SPECIAL;
+    *object_at = -1;
 
     const sr_test_ray* tr = c->tr;
     if (tr && tr->visible) {
@@ -698,6 +702,7 @@ static v4 intersect(const Ctx* c, Ray ray, float max_lambda) {
             seg.radius = tr->radius;
             HitInfo h2 = cylinder_intersect(ray, &seg, max_lambda);
             h2.object.type = OBJECT_TYPE_TEST_RAY_CURVED;
+            h2.part = i;
             if (!h2.is_hit) continue;
             if (!closest.is_hit || h2.dist < closest.dist) closest = h2;
         }
@@ -710,9 +715,18 @@ static v4 intersect(const Ctx* c, Ray ray, float max_lambda) {
         Object o = {so->type, so->index, so->material_index};
         HitInfo hit = intersect_object(c, ray, o, max_lambda);
         if (!hit.is_hit) continue;
-        if (!closest.is_hit || hit.dist < closest.dist) closest = hit;
+        if (!closest.is_hit || hit.dist < closest.dist) {
+            closest = hit;
+            *object_at = i;
+        }
     }
+    return closest;
+}
 
+/* frag:755-822 */
+static v4 intersect(const Ctx* c, Ray ray, float max_lambda) {
+    int object_at;
+    HitInfo closest = intersect_closest(c, ray, max_lambda, &object_at);
     v4 color = V4(0, 0, 0, 0);
     if (closest.is_hit) color = calculate_lighting(c, closest, neg3(ray.dir));
     return color;
@@ -851,6 +865,40 @@ int sro_shade_pixel(const sr_scene* scene, const sr_test_ray* test_ray, const sr
     out_rgba[2] = f.z;
     out_rgba[3] = f.w;
     return s;
+}
+
+/* intersect()'s winner for n chords {o[3], d[3], max_lambda}: winner[i] =
+ * the index in scene.objects[], SRO_HIT_HOLE, SRO_HIT_TEST_RAY_FLAT,
+ * SRO_HIT_TEST_RAY_CURVED or SRO_HIT_NONE; part[i] = the box face (frag:649's
+ * order) or the curved segment, else 0; point_dist[4 i ..] = the point and
+ * its distance (zeros on a miss). */
+int sro_intersect(const sr_scene* scene, const sr_test_ray* test_ray, const float* chords, int n, int32_t* winner,
+                  int32_t* part, float* point_dist) {
+    if (!scene || !chords || !winner || !part || !point_dist || n < 0) return SR_E_INVALID;
+    Ctx c = {scene, test_ray, NULL, NULL, NULL, 0.0f, 0.0f};
+    for (int i = 0; i < n; i++) {
+        const float* q = chords + 7 * (size_t)i;
+        Ray ray = {load_v3(q), load_v3(q + 3)};
+        int object_at;
+        HitInfo h = intersect_closest(&c, ray, q[6], &object_at);
+        float* out = point_dist + 4 * (size_t)i;
+        out[0] = out[1] = out[2] = out[3] = 0.0f;
+        part[i] = 0;
+        if (!h.is_hit) {
+            winner[i] = SRO_HIT_NONE;
+            continue;
+        }
+        winner[i] = h.object.type == OBJECT_TYPE_SPECIAL ? SRO_HIT_HOLE
+                    : h.object.type == OBJECT_TYPE_TEST_RAY_FLAT ? SRO_HIT_TEST_RAY_FLAT
+                    : h.object.type == OBJECT_TYPE_TEST_RAY_CURVED ? SRO_HIT_TEST_RAY_CURVED
+                                                                   : object_at;
+        part[i] = h.part;
+        out[0] = h.intersection_point.x;
+        out[1] = h.intersection_point.y;
+        out[2] = h.intersection_point.z;
+        out[3] = h.dist;
+    }
+    return SR_OK;
 }
 
 typedef struct {

@@ -60,6 +60,17 @@ int sro_shade_pixel(const sr_scene* scene, const sr_test_ray* test_ray, const sr
                     const sr_camera* cam, const sr_params* params, int width, int height,
                     int px, int py, float out_rgba[4]);
 
+/* The closest hit of intersect() (frag:755-814, the one every ray of
+ * sro_render runs) for n chords {origin[3], direction[3], max_lambda} (< 0:
+ * unbounded): see sr_oracle.c. The codes below stand for winners that are not
+ * objects. 0, or SR_E_INVALID. */
+#define SRO_HIT_NONE (-100)
+#define SRO_HIT_HOLE (-1)
+#define SRO_HIT_TEST_RAY_FLAT (-2)
+#define SRO_HIT_TEST_RAY_CURVED (-3)
+int sro_intersect(const sr_scene* scene, const sr_test_ray* test_ray, const float* chords, int n, int32_t* winner,
+                  int32_t* part, float* point_dist);
+
 /* press-R test ray: src/main.cpp:94-124 with MAX_STEPS/MAX_REVOLUTIONS as
  * arguments. Returns the point count (<= max_points written). */
 int sro_test_ray_points(const float pos[3], const float forward[3], int max_steps,

@@ -216,8 +216,10 @@ __device__ __forceinline__ void consider(Hit& best, bool hit, const f3& p, f3 o,
 // 6): an accepted point lies within this of the lateral surface for every
 // chord direction, Sc >= S + |pos|_1 of the chord.
 #ifndef SR_REACH_LAT  // slot_reachable's cylinder margin: lat_margin (1) or round 2's over |d_perp|^2 (0;
-                      // conservative too: 1 measured no faster, profiles/r06/s43)
-#define SR_REACH_LAT 0
+                      // conservative too, and 1 measured no faster, profiles/r06/s43; but it grows as
+                      // Sc^2 / (r |d_perp|^2) and reached a radius-1e-3 cylinder from chords 0.1 Sc beyond
+                      // twice its bounding sphere, tests/test_gpu_bounds.py: 1 since then, as may_hit's)
+#define SR_REACH_LAT 1
 #endif
 __device__ __forceinline__ float lat_margin(float Sc, float r) {
     return fminf(SR_CYL_QMARGIN * Sc * Sc * __builtin_amdgcn_rcpf(r), 2.0f * SR_MU_QUADRATIC * (Sc + r)) * 1.001f;
@@ -2653,7 +2655,9 @@ __device__ __forceinline__ int integrate(const sr_dev_scene* __restrict__ sc, co
         return F2(t.z, t.w);
     };
     // materialise the chord of step i - 1 (its end point from r.u, its start
-    // from r.ro when that is step i - 2, else from up)
+    // from r.ro when that is step i - 2, else from up). bound_probe.h's
+    // sr_probe_end_kernel mirrors these operations (a lambda cannot be called
+    // from there): carry a change here over.
     auto settle_prev = [&](int i) {
         if (im == i - 1) return;
         const f2 p1 = phi_cs(i - 1);
@@ -3251,6 +3255,7 @@ __device__ __forceinline__ void write_pixel(const sr_dev_frame& fr, uint8_t* __r
     if (dbg_steps) dbg_steps[i] = steps;
 }
 
+#include "bound_probe.h"
 }  // namespace
 
 #ifndef SR_MIN_WAVES_PER_EU  // the Makefile's WAVES (7 since round 6)
