@@ -810,6 +810,72 @@ int sr_render_sequence_debug(sr_ctx* ctx, int scene_index, const sr_camera* cam,
                              int width, int height, int row_begin, int row_end, float* dev_rgba32,
                              uint8_t* dev_rgba8, int32_t* dev_steps, sr_stream stream);
 
+/* ---- Ray queries (not in the reference, whose every ray starts at the one
+ * camera position). A trace launch walks rays the caller supplies, each with
+ * an origin of its own: thin-lens depth of field, stereo panoramas, calibrated
+ * lens warps, probes inside the scene, line-of-sight tests along bent rays,
+ * the press-R test ray on the device.
+ *
+ * Definition. Ray i of a trace launch has origin O = origins[3 i .. 3 i + 2]
+ * and direction V = dirs[3 i .. 3 i + 2]; V need not be normalised. Its
+ * results are, bit for bit, those of pixel (0, 0) of a 1 x 1 pinhole
+ * (RECTILINEAR) frame of fov 90 whose camera position is O and whose camera
+ * axes' columns are (0, 0, V), with crosshair = 0 and percent_black < 0, the
+ * context's current scene, test ray, background and texture array, and the
+ * call's params. So:
+ *   - the direction the walk starts with is normalize((0 * 0 + 0 * 0) + V * 1)
+ *     in binary32: normalize(V) with any -0 component of V made +0;
+ *   - nv, u, tv and du are the shader's expressions (frag:883-889) on O and
+ *     that direction, per ray; the radial test |dot(rd, nv)| >= 1 - 1e-7, the
+ *     reseed beyond 1 / u_f, capture, translucency, the test-ray overlay and
+ *     the flat tail apply unchanged;
+ *   - non-finite or zero O or V, an origin at or inside the horizon or at the
+ *     centre are not rejected: they give what the reference's arithmetic gives;
+ *   - params->raytrace_type is SR_RAYTRACE_CURVED or SR_RAYTRACE_FLAT (a ray
+ *     has no uv: the split modes are SR_E_INVALID); crosshair, percent_black
+ *     and curved_percentage are ignored; max_steps, max_revolutions, u_f and
+ *     filter_mode are honoured, including the rule that max_revolutions <= 0
+ *     or a negative or NaN u_f runs the reference's own loop;
+ *   - sr_set_projection, sr_set_split, sr_set_latency_mode and a scene
+ *     sequence do not matter to a trace launch; culling applies (never a
+ *     result);
+ *   - the launch reads and writes no pixel state: a retained frame stays
+ *     valid across it (sr_can_reshade, sr_reshade and sr_pick_map see the
+ *     last frame launch), learned launch orders stay untouched, and
+ *     sr_diag_counters keeps its meaning.
+ * A ray's result does not depend on the other rays of the launch or on their
+ * order. */
+#define SR_TRACE_MAX_RAYS (1 << 28)
+/* Inputs: device pointers to n_rays packed xyz triples (12 bytes per ray, 4-byte
+ * aligned). Outputs: device pointers, each dense with one entry per ray and
+ * 4-byte aligned, any of them NULL but not all: float FragColor (16 bytes per
+ * ray); RGBA8 by the frames' conversion (NaN, +inf, -inf store 0, 255, 0);
+ * the executed steps; and sr_pick_map's code (an index into scene.objects[]
+ * or SR_PICK_*; never SR_PICK_NONE): the first surface on the ray's walk that
+ * is not a single-sided surface seen from behind. A launch that asks for
+ * dev_ids alone may end each ray at that surface; the ids are the same either
+ * way. n_rays == 0: SR_OK, nothing written. Asynchronous on `stream`, no host
+ * wait, ordered like every launch of the context. Checked before anything is
+ * launched, nothing written: SR_E_INVALID for a null context or params,
+ * n_rays < 0 or above SR_TRACE_MAX_RAYS, null or misaligned inputs, misaligned
+ * outputs, all outputs NULL, a split mode or unknown raytrace_type or
+ * filter_mode, max_steps outside 0 .. SR_MAX_STEPS; SR_E_NOT_READY without a
+ * scene. */
+int sr_trace_rays(sr_ctx* ctx, const float* dev_origins, const float* dev_dirs, int n_rays,
+                  const sr_params* params, float* dev_rgba32, uint8_t* dev_rgba8,
+                  int32_t* dev_steps, int32_t* dev_ids, sr_stream stream);
+/* Host only, no context: the rays the frame kernels start with, for rows
+ * [row_begin, row_end) of a plain width x height frame, row-major from
+ * row_begin (3 floats per pixel in each of origins and dirs, host memory).
+ * Pixel (px, py): O = the camera's position, V = axes * L in binary32, (c0 *
+ * L.x + c1 * L.y) + c2 * L.z with L sr_projection_dir's own; a pixel without
+ * a ray (the fisheye beyond PI) gets V = (NaN, NaN, NaN). Traced, these rays
+ * give the frame's pixels (where no component of V is -0: see above).
+ * SR_E_INVALID for null arguments, an unknown projection, sizes <= 0 or above
+ * INT32_MAX / 2, or rows outside 0 <= row_begin <= row_end <= height. */
+int sr_camera_rays(const sr_camera* cam, int projection, int width, int height,
+                   int row_begin, int row_end, float* origins, float* dirs);
+
 /* Rows a sr_render_blocks call with these arguments writes. */
 int sr_blocks_row_count(int height, int block_rows, int block_first, int block_step);
 

@@ -19,7 +19,7 @@ name is not a Python identifier).
 """
 from . import abi, assets, dist, scenes  # noqa: F401
 
-__all__ = ["abi", "assets", "dist", "scenes", "Renderer"]
+__all__ = ["abi", "assets", "dist", "scenes", "Renderer", "camera_rays"]
 
 
 def __getattr__(name):
@@ -27,4 +27,8 @@ def __getattr__(name):
         from .renderer import Renderer
 
         return Renderer
+    if name == "camera_rays":
+        from .renderer import camera_rays
+
+        return camera_rays
     raise AttributeError(name)

@@ -230,6 +230,8 @@ SIGNATURES = {
     "sr_render_sequence_block_list": (_i, [_p, _i, C.POINTER(Camera), _i, C.POINTER(Params), _i, _i, _i, C.POINTER(_i),
                                            _i, _i, _p, C.c_size_t, C.c_size_t, _p]),
     "sr_render_sequence_debug": (_i, [_p, _i, C.POINTER(Camera), C.POINTER(Params), _i, _i, _i, _i, _p, _p, _p, _p]),
+    "sr_trace_rays": (_i, [_p, _p, _p, _i, C.POINTER(Params), _p, _p, _p, _p, _p]),
+    "sr_camera_rays": (_i, [C.POINTER(Camera), _i, _i, _i, _i, _i, _p, _p]),
 }
 # sr_set_projection's values (sr.h "Projections")
 PROJECTION_RECTILINEAR, PROJECTION_EQUIRECT, PROJECTION_FISHEYE = 0, 1, 2
@@ -239,6 +241,8 @@ PROJECTIONS = {"rectilinear": PROJECTION_RECTILINEAR, "equirect": PROJECTION_EQU
 SINCE_PROJECTIONS = ("sr_set_projection", "sr_get_projection", "sr_projection_dir")
 SINCE_SEQUENCES = ("sr_set_scene_sequence", "sr_scene_sequence_length", "sr_render_sequence",
                    "sr_render_sequence_block_list", "sr_render_sequence_debug")
+SINCE_TRACE = ("sr_trace_rays", "sr_camera_rays")
+TRACE_MAX_RAYS = 1 << 28  # rays of one trace launch (sr.h "Ray queries")
 MAX_SEQUENCE = 256  # scenes of a sequence (sr.h "Scene sequences")
 # sr_pick_map's codes below the indices into scene.objects[]
 PICK_SKY, PICK_HOLE, PICK_TEST_RAY_FLAT, PICK_TEST_RAY_CURVED, PICK_NONE = -1, -2, -3, -4, -5
@@ -285,7 +289,8 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
         raise FileNotFoundError(f"{p} not built; run __graft_entry__.build() or make -C schwarzschild-raytracer_amd")
     lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **EXTRA_SIGNATURES}.items():
-        if (name in EXTRA_SIGNATURES or name in SINCE_PROJECTIONS or name in SINCE_SEQUENCES) and not hasattr(lib, name):
+        if (name in EXTRA_SIGNATURES or name in SINCE_PROJECTIONS or name in SINCE_SEQUENCES or
+                name in SINCE_TRACE) and not hasattr(lib, name):
             continue  # debug tooling and newer calls an older library (a bisection build) may lack
         fn = getattr(lib, name)
         fn.restype = res
@@ -319,6 +324,24 @@ def projection_dir(projection: int, fov: float, uv_width: int, uv_height: int, p
     if rc < 0:
         raise SRError(rc, "sr_projection_dir")
     return out if rc == 1 else None
+
+
+def camera_rays(cam: Camera, projection, width: int, height: int, row_begin: int = 0, row_end: int | None = None):
+    """sr_camera_rays: the rays the frame kernels start with for rows
+    [row_begin, row_end) of a width x height frame under `projection`
+    (PROJECTION_* or its name) -> (origins, dirs), float32 [rows, width, 3]
+    host arrays; a pixel without a ray has a NaN direction. Host only."""
+    import numpy as np
+
+    if isinstance(projection, str):
+        projection = PROJECTIONS[projection]
+    row_end = height if row_end is None else row_end
+    rows = max(int(row_end) - int(row_begin), 0)
+    o = np.empty((rows, int(width), 3), dtype=np.float32)
+    d = np.empty((rows, int(width), 3), dtype=np.float32)
+    check(load().sr_camera_rays(C.byref(cam), int(projection), int(width), int(height), int(row_begin), int(row_end),
+                                o.ctypes.data, d.ctypes.data), "sr_camera_rays")
+    return o, d
 
 
 def write_png(path, frame, flip_rows: bool = True) -> None:

@@ -337,6 +337,22 @@ typedef struct {
 // tests/test_low_energy_bounds.py (the app's MAX_STEPS 100 at up to three
 // revolutions: 0.1885); coarser schedules exclude nothing
 #define SR_XLOW_DPHI_MAX 0.2f
+// the largest step angle at which a trace launch (sr_trace_rays) culls; coarser
+// schedules run the reference's loop. The outward lanes' exclusions
+// (geodesic.hip outward_clear) rest on "u' < 0 at u < 0.6 keeps u falling",
+// which is the orbit's property and RK4's only while a step's stages stay near
+// it: with v = u' < 0 the stage values are u + (h / 2) v or lower, where u'' =
+// -u + 1.5 u^2 is about 1.5 (h v / 2)^2 > 0, so k3 = v (1 - (3 / 16) h^3 |v|)
+// and k4 = v (1 - (3 / 8) h^3 |v|) to leading order, and the step lowers u
+// while (3 / 8) h^3 |v| < 1. |v| = u |cot(angle to the radius)| is at most 0.6
+// x 2236 (the radial test's 1 - 1e-7 sends anything closer to the flat tail),
+// so h <= 0.1 keeps (3 / 8) h^3 |v| below 0.51. A frame's rays come within
+// that angle of the outward radius only under a panorama's or a fisheye's
+// backward pixels; a trace launch's rays point anywhere. Measured: at 5 to 12
+// steps of two revolutions (1 to 2.5 rad) such rays are flung back into the
+// hole by the reference's arithmetic and the culled loop missed it, at 25
+// steps (0.5 rad) and finer none did (DESIGN.md §5 "Ray queries").
+#define SR_TRACE_DPHI_MAX 0.1f
 
 // the inner black-hole window's margins (precompute.cpp derive_frame, geodesic.hip)
 #define SR_BH_G2 1.5e-3

@@ -4047,3 +4047,129 @@ extern "C" hipError_t sr_launch_geodesic_seq(const sr_dev_scene* sc, const float
     if (ev4) (void)hipEventRecord(ev4[3], stream);
     return hipGetLastError();
 }
+
+// ---- ray queries (sr.h "Ray queries"): caller-supplied rays, one lane each
+
+// A trace launch's grid-stride grid, in SR_WG-lane workgroups: one ray per
+// lane up to this many workgroups, a stride beyond
+#ifndef SR_TRACE_GROUPS
+#define SR_TRACE_GROUPS 65536u
+#endif
+// Ray w of the launch: origin O = origins[3 w ..], direction V = dirs[3 w ..],
+// by definition pixel (0, 0) of the 1 x 1 pinhole frame of fov 90 with the
+// camera at O and the axes columns (0, 0, V): uv = (0, 0), ray_forward = 1, so
+// init_pixel's mv(axes, L) is (0 x 0 + 0 x 0) + V x 1 = +0 + V (a -0 of V
+// becomes +0), and its camera-only values are build_start's expressions on O,
+// here per ray. No percent_black, no crosshair, no split modes (the host
+// rejects them: a ray has no uv). Then sr_resume_kernel's rounds from step 0
+// with budget_init at the lane's own anchor O (DESIGN.md §5 "Ray queries" has
+// the audit of what the culling assumes about a ray's start: fr.win_ok is 0
+// here, the host cannot see the origins), finish_ray, and the requested
+// outputs. The lanes of a wave are unrelated rays: the step index is per
+// lane (integrate's RECORD = false form) and nothing derived from a ray is
+// pinned to an SGPR. ids: sr_pick_kernel's code, from the first hit that is
+// not OP_ZERO (the step loop skips those) or from the ray's end; a launch of
+// ids alone (ids_only) ends each ray there.
+// Emitted where sr_launch_trace instantiates it: after every other kernel.
+// pick_flat's rule in line (a call of the noinline function from this
+// kernel's divergent rounds does not compile: "illegal VGPR to SGPR copy")
+__device__ __forceinline__ int trace_pick_flat(const sr_dev_scene* __restrict__ sc, const float* __restrict__ segs,
+                                               const sr_dev_frame& fr, const Tex& tx, f3 ro, f3 rd) {
+    const Hit h = closest_hit_all(sc, segs, ro, rd, -1.0f);
+    if (h.slot == SLOT_NONE) return PICK_SKY;
+    return hit_opacity(sc, fr, tx, h, -rd, true) == OP_ZERO ? PICK_SKY : pick_code(h.slot);
+}
+template <bool CULL, bool TR = false>
+__global__ __launch_bounds__(SR_WG) void sr_trace_kernel(const sr_dev_scene* __restrict__ sc,
+                                                      const float4* __restrict__ tbl,
+                                                      const float* __restrict__ segs,
+                                                      const uint32_t* __restrict__ bg,
+                                                      const uint32_t* __restrict__ arr, sr_dev_frame fr,
+                                                      const float* __restrict__ origins,
+                                                      const float* __restrict__ dirs, int n_rays,
+                                                      float* __restrict__ out_rgba, uint32_t* __restrict__ out_rgba8,
+                                                      int32_t* __restrict__ out_steps, int32_t* __restrict__ out_ids) {
+    const PS ps{nullptr, 0};
+    Tex tx;
+    tx.bg = bg;
+    tx.arr = arr;
+    tx.opq = nullptr;
+    const bool ids_only = !out_rgba && !out_rgba8 && !out_steps;
+    for (size_t w = (size_t)blockIdx.x * SR_WG + threadIdx.x; w < (size_t)n_rays; w += (size_t)gridDim.x * SR_WG) {
+        Ray r;
+        r.ro = ld3(origins + 3 * w);
+        r.rd = nrm(F3(0.0f, 0.0f, 0.0f) + ld3(dirs + 3 * w));
+        r.nv = nrm(r.ro);
+        r.tv = F3(0.0f, 0.0f, 0.0f);
+        r.u = r.du = 0.0f;
+        r.steps = 0;
+        r.i = 0;
+        int st = -1;
+        if (fr.raytrace_type == SR_RAYTRACE_FLAT || fabsf(dot(r.rd, r.nv)) >= 1.0f - SR_EPS) {
+            st = ST_FLAT;
+        } else {  // frag:883-889
+            r.tv = nrm(cross(cross(r.nv, r.rd), r.nv));
+            r.u = 1.0f / len(r.ro);
+            r.du = -r.u * dot(r.rd, r.nv) / dot(r.rd, r.tv);
+        }
+        f4 frag = F4(0.0f, 0.0f, 0.0f, 0.0f);
+        int code = PICK_NONE;
+        bool picked = false;
+        HitLog log{ps, 0};  // RECORD = false: nothing is logged
+        if (st < 0) {
+            for (;;) {  // rounds: integrate to the next hit, shade, resume if not opaque
+                Hit hit = no_hit();
+                st = integrate<CULL, false, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, TR>(sc, segs, tbl, fr, tx, r,
+                                                                                                 hit, log);
+                if (st != ST_HIT) break;
+                if (!picked) code = pick_code(hit.slot);
+                picked = true;
+                if (ids_only) break;
+                const f4 c = shade(sc, fr, tx, hit, -r.rd);
+                frag = frag + c;
+                if (c.w == 1.0f) break;  // frag:932
+                r.i++;
+            }
+        }
+        if (st != ST_HIT) {
+            if (!picked && out_ids) code = st == ST_FLAT ? trace_pick_flat(sc, segs, fr, tx, r.ro, r.rd) : PICK_SKY;
+            if (!ids_only) finish_ray(sc, segs, fr, tx, st, r.ro, r.rd, frag);
+        }
+        if (out_rgba) {
+            out_rgba[4 * w + 0] = frag.x;
+            out_rgba[4 * w + 1] = frag.y;
+            out_rgba[4 * w + 2] = frag.z;
+            out_rgba[4 * w + 3] = frag.w;
+        }
+        if (out_rgba8) out_rgba8[w] = unorm8(frag.x) | (unorm8(frag.y) << 8) | (unorm8(frag.z) << 16) | (unorm8(frag.w) << 24);
+        if (out_steps) out_steps[w] = r.steps;
+        if (out_ids) out_ids[w] = code;
+    }
+}
+
+extern "C" hipError_t sr_launch_trace(const sr_dev_scene* sc, const float4* tbl, const float* segs, const uint32_t* bg,
+                                      const uint32_t* arr, const sr_dev_frame* fr, const float* origins,
+                                      const float* dirs, int n_rays, float* out_rgba, uint8_t* out_rgba8,
+                                      int32_t* out_steps, int32_t* out_ids, hipStream_t stream) {
+    if (n_rays < 0 || n_rays > SR_TRACE_MAX_RAYS) return hipErrorInvalidValue;
+    if (n_rays == 0) return hipSuccess;
+    if (!sc || !tbl || !fr || !origins || !dirs || (!out_rgba && !out_rgba8 && !out_steps && !out_ids))
+        return hipErrorInvalidValue;
+    const bool cull = fr->cull != 0;
+    const bool tr = cull && fr->tr_visible != 0;
+    // cylinders with direction tests beyond what the instantiation handles (sr_launch_geodesic)
+    if (cull && fr->num_budget_cyl > SR_NC_KERNEL) return hipErrorInvalidValue;
+    const unsigned groups = ((unsigned)n_rays + SR_WG - 1u) / SR_WG;
+    const dim3 grid(groups < SR_TRACE_GROUPS ? groups : SR_TRACE_GROUPS);
+    const auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, origins, dirs, n_rays,
+                           out_rgba, reinterpret_cast<uint32_t*>(out_rgba8), out_steps, out_ids);
+    };
+    if (tr)  // the overlay budgeted, as the resume kernel's
+        go(sr_trace_kernel<true, true>);
+    else if (cull)
+        go(sr_trace_kernel<true>);
+    else  // the reference's loop
+        go(sr_trace_kernel<false>);
+    return hipGetLastError();
+}

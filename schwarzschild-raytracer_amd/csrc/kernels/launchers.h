@@ -36,6 +36,12 @@ hipError_t sr_launch_reshade(const sr_dev_scene* sc, const float4* tbl, const fl
 // one object code per pixel from that state (sr_pick_map)
 hipError_t sr_launch_pick(const sr_dev_scene* sc, const float* segs, const sr_dev_frame* fr, const float* ps,
                           size_t ps_n, int32_t* out, size_t pitch, size_t frame_stride, hipStream_t stream);
+// caller-supplied rays, one lane each (sr_trace_rays; sr.h "Ray queries"): fr is a 1 x 1 frame's struct with
+// win_ok = 0, of which the schedule, the margins, the exclusions and the texture sizes are read; no pixel state
+hipError_t sr_launch_trace(const sr_dev_scene* sc, const float4* tbl, const float* segs, const uint32_t* bg,
+                           const uint32_t* arr, const sr_dev_frame* fr, const float* origins, const float* dirs,
+                           int n_rays, float* out_rgba, uint8_t* out_rgba8, int32_t* out_steps, int32_t* out_ids,
+                           hipStream_t stream);
 
 // ---- assemble.hip
 hipError_t sr_assemble_blocks_device(const uint8_t* stacked, size_t rank_stride, size_t in_frame_stride,

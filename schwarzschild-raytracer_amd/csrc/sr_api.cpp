@@ -1407,6 +1407,68 @@ int sr_pick_map(sr_ctx* c, int32_t* ids, size_t pitch, size_t frame_stride, sr_s
                   s);
 }
 
+// ---- ray queries (sr.h): caller-supplied rays through the current scene
+
+int sr_trace_rays(sr_ctx* c, const float* dev_origins, const float* dev_dirs, int n_rays, const sr_params* p,
+                  float* dev_rgba32, uint8_t* dev_rgba8, int32_t* dev_steps, int32_t* dev_ids, sr_stream stream) {
+    if (!c) return SR_E_INVALID;
+    if (!c->scene_set) return SR_E_NOT_READY;
+    if (n_rays < 0 || n_rays > SR_TRACE_MAX_RAYS) return SR_E_INVALID;
+    // the definition's frame: 1 x 1, fov 90; the camera's position and forward
+    // axis are each ray's own (geodesic.hip sr_trace_kernel), the rest is unread
+    sr_camera cam;
+    std::memset(&cam, 0, sizeof cam);
+    cam.fov = 90.0f;
+    int rc = sr_pre::check_frame_args(&cam, p, 1, 1);
+    if (rc != SR_OK) return rc;
+    if (p->raytrace_type != SR_RAYTRACE_CURVED && p->raytrace_type != SR_RAYTRACE_FLAT) return SR_E_INVALID;  // no uv
+    if (n_rays == 0) return SR_OK;
+    const auto misaligned = [](const void* q) { return ((uintptr_t)q & 3) != 0; };
+    if (!dev_origins || !dev_dirs || misaligned(dev_origins) || misaligned(dev_dirs)) return SR_E_INVALID;
+    if (!dev_rgba32 && !dev_rgba8 && !dev_steps && !dev_ids) return SR_E_INVALID;
+    if (misaligned(dev_rgba32) || misaligned(dev_rgba8) || misaligned(dev_steps) || misaligned(dev_ids))
+        return SR_E_INVALID;
+    sr_params pp = *p;
+    pp.crosshair = 0;
+    pp.percent_black = -1.0f;
+    sr_dev_frame fr;
+    sr_pre::derive_frame({&cam, 1, &pp, 1, 1, 1, nullptr, c->cull, SR_PROJECTION_RECTILINEAR}, c->h_scene, fr);
+    // the one launch constant whose premise is the camera position ("chord
+    // origins within r = 100"): the host cannot see the origins
+    fr.win_ok = 0;
+    // and the one about its direction: a frame's rays leave a camera that
+    // looks at the scene, a trace launch's point anywhere, also along the
+    // outward radius, where a coarse schedule's RK4 steps stop following the
+    // orbit the outward lanes' exclusions assume (device_scene.h)
+    if (!(fr.max_dphi <= SR_TRACE_DPHI_MAX)) fr.cull = 0;
+    if (!(c->xc_uf == fr.u_f && c->xc_dphi == fr.max_dphi)) {  // as build_frame
+        sr_pre::low_energy_exclusions(c->h_scene, fr.u_f, fr.max_dphi, c->xc_need, c->xc_peri);
+        c->xc_uf = fr.u_f;
+        c->xc_dphi = fr.max_dphi;
+    }
+    std::memcpy(fr.xlow_need, c->xc_need, sizeof fr.xlow_need);
+    std::memcpy(fr.xperi_e, c->xc_peri, sizeof fr.xperi_e);
+    fr.bg_w = c->bg_w;
+    fr.bg_h = c->bg_h;
+    fr.arr_w = c->arr_w;
+    fr.arr_h = c->arr_h;
+    fr.arr_layers = c->arr_layers;
+    fr.fast_unroll = SR_FAST_UNROLL_DEFAULT;
+    fr.tiles = 1;
+    fr.nrows = 1;
+    fr.block_rows = 1;
+    // no pixel state, no launch order, no retained frame: the context's stay as they are
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    const float4* tbl = nullptr;
+    rc = ensure_table(c, p->max_steps, p->max_revolutions, s, &tbl);
+    if (rc != SR_OK) return rc;
+    return finish(c, sr_launch_trace(c->d_scene, tbl, c->d_segs, c->d_bg, c->d_arr, &fr, dev_origins, dev_dirs, n_rays,
+                                     dev_rgba32, dev_rgba8, dev_steps, dev_ids, s),
+                  s);
+}
+
 int sr_abi_struct_sizes(size_t* out, int n) {
     const size_t sz[6] = {sizeof(sr_camera), sizeof(sr_params), sizeof(sr_scene),
                           sizeof(sr_test_ray), sizeof(sr_material), sizeof(sr_light)};
@@ -1482,6 +1544,29 @@ int sr_projection_dir(int projection, float fov, int uv_width, int uv_height, in
         return SR_E_INVALID;
     }
     return ray ? 1 : 0;
+}
+
+int sr_camera_rays(const sr_camera* cam, int projection, int width, int height, int row_begin, int row_end,
+                   float* origins, float* dirs) {
+    if (!cam || !origins || !dirs || width <= 0 || height <= 0 || bad_rows(row_begin, row_end, height))
+        return SR_E_INVALID;
+    if (width > INT32_MAX / 2 || height > INT32_MAX / 2) return SR_E_INVALID;
+    if (projection < SR_PROJECTION_RECTILINEAR || projection > SR_PROJECTION_FISHEYE) return SR_E_INVALID;
+    const float* a = cam->transform.axes;
+    size_t k = 0;
+    for (int py = row_begin; py < row_end; py++) {
+        for (int px = 0; px < width; px++, k += 3) {
+            float L[3];
+            const int ray = sr_projection_dir(projection, cam->fov, width, height, px, py, L);
+            if (ray < 0) return ray;
+            for (int j = 0; j < 3; j++) {
+                origins[k + j] = cam->transform.pos[j];
+                // init_pixel's mv(axes, L) (geodesic.hip), before its normalize
+                dirs[k + j] = ray ? (a[j] * L[0] + a[3 + j] * L[1]) + a[6 + j] * L[2] : NAN;
+            }
+        }
+    }
+    return SR_OK;
 }
 
 // Not in sr.h's public set: the launch codes order_tiles wrote at the end

@@ -13,6 +13,14 @@ import numpy as np
 from . import abi
 
 
+def camera_rays(cam: abi.Camera, projection, w: int, h: int):
+    """The rays the frame kernels start with (sr_camera_rays): host float32
+    arrays (origins, dirs) of shape [h, w, 3] for the w x h frame of `cam`
+    under `projection` (abi.PROJECTION_* or its name); a pixel without a ray
+    has a NaN direction. Renderer.trace_rays of them gives the frame's pixels."""
+    return abi.camera_rays(cam, projection, w, h)
+
+
 class Renderer:
     """One sr_ctx bound to one HIP device (the reference's single GL program)."""
 
@@ -509,6 +517,43 @@ class Renderer:
         if m.dim() == 3:
             m = m[frame]
         return int(m[int(y), int(x)].item())
+
+    # ---- ray queries (sr.h): caller-supplied rays through the current scene ----
+    def trace_rays(self, origins, dirs, params: abi.Params, rgba32: bool = False, rgba8: bool = True,
+                   steps: bool = False, ids: bool = False, stream=None):
+        """sr_trace_rays: ray i from origins[i] along dirs[i] ((N, 3) float32
+        tensors on this device; the directions need not be normalised) -> a
+        dict of the requested tensors, one entry per ray: "rgba32" float32
+        [N, 4] FragColor, "rgba8" uint8 [N, 4], "steps" int32 [N] and "ids"
+        int32 [N] (pick_map's codes). Asynchronous."""
+        t = self.torch
+        for a in (origins, dirs):
+            assert a.dtype == t.float32 and a.dim() == 2 and a.shape[1] == 3 and a.is_contiguous()
+            assert a.device == self.tdev
+        n = int(origins.shape[0])
+        assert int(dirs.shape[0]) == n
+        if not (rgba32 or rgba8 or steps or ids):
+            raise ValueError("trace_rays: no output requested")
+        out = {}
+        if rgba32:
+            out["rgba32"] = t.empty((n, 4), dtype=t.float32, device=self.tdev)
+        if rgba8:
+            out["rgba8"] = t.empty((n, 4), dtype=t.uint8, device=self.tdev)
+        if steps:
+            out["steps"] = t.empty((n,), dtype=t.int32, device=self.tdev)
+        if ids:
+            out["ids"] = t.empty((n,), dtype=t.int32, device=self.tdev)
+
+        def ptr(key):
+            return C.c_void_p(out[key].data_ptr()) if key in out and n else None
+
+        abi.check(
+            self.lib.sr_trace_rays(self.ctx, C.c_void_p(origins.data_ptr()) if n else None,
+                                   C.c_void_p(dirs.data_ptr()) if n else None, n, C.byref(params), ptr("rgba32"),
+                                   ptr("rgba8"), ptr("steps"), ptr("ids"), self._stream(stream)),
+            "sr_trace_rays",
+        )
+        return out
 
     def close(self) -> None:
         if self.ctx:

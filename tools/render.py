@@ -14,6 +14,9 @@ hyperbolic trajectory (src/main.cpp:404-410) in batched launches.
   python tools/render.py --projection equirect --fov 360 --width 2048 --height 1024 --out pano.png
   python tools/render.py --projection fisheye --fov 180 --width 1080 --height 1080 --out dome.png
                                   (sr_set_projection: a 360 degree panorama, a dome master)
+  python tools/render.py --aperture 0.15 --focus 5.4 --lens-samples 16 --out dof.png
+                                  (thin-lens depth of field: per-ray origins on the lens disk, traced with
+                                   sr_trace_rays, the samples' frames averaged)
   python tools/render.py --orbit-frames 48 --out orbit_%02d.png
                                   (the default scene's sphere on a circular orbit: the scenes as one
                                    sequence, sr_set_scene_sequence, rendered 32 frames per launch)
@@ -27,6 +30,42 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 MODES = {"curved": 0, "flat": 1, "half_width": 2, "half_height": 3}
+
+
+def thin_lens_frame(pkg, r, cam, params, width, height, aperture, focus, samples, seed=0):
+    """Thin-lens depth of field through Renderer.trace_rays -> uint8 [height,
+    width, 4] on the device. Every pixel's pinhole ray (sr_camera_rays) meets
+    the plane of focus at P = O + focus * V / |V|; sample k starts at a point
+    O + aperture * (x c0 + y c1) of the lens, (x, y) uniform on the unit disk
+    (c0, c1: the camera's right and up axes), and heads for P. The rays are
+    made with torch on the device; the `samples` frames are averaged with
+    sr_accum_resolve's rounding, (sum + n / 2) / n per channel. aperture 0:
+    the pinhole's own rays, so one sample is the plain render's frame byte for
+    byte (the crosshair and the noise mask apart, which a trace launch does
+    not draw)."""
+    import numpy as np
+    import torch
+
+    O, V = pkg.camera_rays(cam, "rectilinear", width, height)
+    O = torch.from_numpy(O.reshape(-1, 3)).to(r.tdev)
+    V = torch.from_numpy(V.reshape(-1, 3)).to(r.tdev)
+    n = O.shape[0]
+    ax = torch.tensor(np.array(list(cam.transform.axes), dtype=np.float32).reshape(3, 3), device=r.tdev)
+    P = O + float(focus) * V / V.norm(dim=1, keepdim=True)
+    gen = torch.Generator(device=r.tdev)
+    gen.manual_seed(int(seed))
+    total = torch.zeros((n, 4), dtype=torch.int32, device=r.tdev)
+    for _ in range(int(samples)):
+        if aperture > 0.0:
+            rad = float(aperture) * torch.sqrt(torch.rand(n, generator=gen, device=r.tdev))
+            ang = 2.0 * math.pi * torch.rand(n, generator=gen, device=r.tdev)
+            o = O + (rad * torch.cos(ang))[:, None] * ax[0] + (rad * torch.sin(ang))[:, None] * ax[1]
+            o, v = o.contiguous(), (P - o).contiguous()
+        else:
+            o, v = O, V
+        total += r.trace_rays(o, v, params)["rgba8"].to(torch.int32)
+    k = int(samples)
+    return ((total + k // 2) // k).to(torch.uint8).reshape(height, width, 4)
 
 
 def main():
@@ -60,7 +99,21 @@ def main():
     ap.add_argument("--orbit-frames", type=int, default=0, metavar="N",
                     help="N frames (1 .. 256) of the default scene with its sphere on a circular orbit of its own radius "
                          "about the hole, rendered through one scene sequence (sr_render_sequence; --out with %%d)")
+    ap.add_argument("--aperture", type=float, default=None, metavar="R",
+                    help="thin-lens depth of field: the lens radius in scene units (0: a pinhole); the frame is "
+                         "traced ray by ray (sr_trace_rays) from origins jittered on the lens disk")
+    ap.add_argument("--focus", type=float, default=10.0, metavar="D",
+                    help="--aperture: the distance along each pixel's pinhole ray that stays sharp")
+    ap.add_argument("--lens-samples", type=int, default=16, metavar="K", help="--aperture: lens samples per pixel")
     args = ap.parse_args()
+    if args.aperture is not None:
+        if (args.flyby > 0 or args.adaptive is not None or args.progressive is not None or args.orbit_frames or
+                args.ssaa != 1 or args.projection != "rectilinear" or args.crosshair or args.percent_black >= 0.0 or
+                args.mode not in ("curved", "flat")):
+            ap.error("--aperture renders one pinhole frame of traced rays: no other mode, crosshair, noise mask or "
+                     "split screen")
+        if args.aperture < 0.0 or args.lens_samples < 1:
+            ap.error("--aperture takes R >= 0 and --lens-samples K >= 1")
     if args.orbit_frames and (args.flyby > 0 or args.adaptive is not None or args.progressive is not None):
         ap.error("--orbit-frames is a mode of its own: no --flyby, --adaptive or --progressive")
     if not 0 <= args.orbit_frames <= 256:
@@ -96,7 +149,12 @@ def main():
             cam.fov = args.fov
         return cam
 
-    if args.orbit_frames:
+    if args.aperture is not None:
+        frame = thin_lens_frame(pkg, r, camera(), params, W, H, args.aperture, args.focus, args.lens_samples)
+        torch.cuda.synchronize()
+        abi.write_png(args.out, frame.cpu().numpy())
+        print(f"wrote {args.out} ({args.lens_samples} lens samples)")
+    elif args.orbit_frames:
         n = args.orbit_frames
         scenes = []
         for k in range(n):  # the sphere once around the hole, in the plane and at the distance it starts at
