@@ -67,7 +67,7 @@
 // Objects held in per-lane budget slots (slot 0 is the black hole): every
 // object of a full scene (SR_MAX_OBJECTS). The integrate kernel is
 // instantiated for 6 (the default scene), 8 and all 21 slots
-// (geodesic.hip sr_launch_geodesic).
+// (kernels/dispatch.h).
 #ifndef SR_MAX_BUDGET
 #define SR_MAX_BUDGET SR_MAX_OBJECTS
 #endif
@@ -275,7 +275,7 @@ typedef struct {
     // inside), where the black hole's u window holds (geodesic.hip SR_BH_WINDOW)
     int32_t win_ok;
     // the scene's budget slots (sr_dev_scene.num_budget): picks the integrate
-    // kernel's slot capacity (geodesic.hip SR_NB_SMALL)
+    // kernel's slot capacity (kernels/dispatch.h SR_NB_SMALL)
     int32_t num_budget;
     // the scene's budgeted cylinders (popcount of sr_dev_scene.budget_cyl_mask;
     // the small instantiation handles SR_NC_SMALL)
@@ -311,7 +311,7 @@ typedef struct {
     // (geodesic.hip SR_XPERI, precompute.cpp xperi_e); -1: never excluded
     float xperi_e[SR_MAX_BUDGET];
     // the context's projection (sr_set_projection, SR_PROJECTION_*): picks the
-    // integrate kernel's instantiation (geodesic.hip sr_launch_geodesic); no
+    // integrate kernel's instantiation (kernels/dispatch.h); no
     // kernel reads it
     int32_t projection;
     // per frame of the batch, cam[f]'s fov / 360 * PI: the half angle behind

@@ -25,6 +25,7 @@ __device__ __forceinline__ float4 ldc(const sr_cfloat4* p) {
 }
 
 #include "../device_scene.h"
+#include "dispatch.h"
 #include "launchers.h"
 #include "sr/projection.hpp"
 
@@ -655,22 +656,8 @@ __device__ __forceinline__ float nmin(float m, float e) { return __builtin_eleme
 #endif
 #define SR_WG_PER_TILE (256 / SR_WG)
 #define SR_E_STRIDE SR_WG
-// Budgeted cylinders whose nearly parallel chords the kernel handles apart
-// (chord_parallel, slab budgets, the cylinder-plane fast loops) in the
-// general and large instantiations and the resume kernel: none since round 6
-// (precompute.cpp SR_CYL_DIRFREE: the lateral margin holds for every direction);
-// SR_MAX_CYLINDERS for a host built with SR_CYL_DIRFREE=0
-#ifndef SR_NC_KERNEL
-#define SR_NC_KERNEL 0
-#endif
 #ifndef SR_AHEAD
 #define SR_AHEAD 2.0f
-#endif
-#ifndef SR_FAST_UNROLL  // fast-loop steps per iteration (1 .. 4; the step table has 4 padding entries);
-                        // the latency mode's instantiation runs 2 (sr_set_latency_mode). 4 since round 6:
-                        // at 7 waves per SIMD 0.5 % more frames per second than 3 in two A/Bs
-                        // (profiles/r06/s18, s19), one frame alone level
-#define SR_FAST_UNROLL SR_FAST_UNROLL_DEFAULT
 #endif
 #ifndef SR_AHEAD_T
 #define SR_AHEAD_T 1.0f
@@ -3261,23 +3248,9 @@ __device__ __forceinline__ void write_pixel(const sr_dev_frame& fr, uint8_t* __r
 #ifndef SR_MIN_WAVES_PER_EU  // the Makefile's WAVES (7 since round 6)
 #define SR_MIN_WAVES_PER_EU 7
 #endif
-#ifndef SR_NB_SMALL
-#define SR_NB_SMALL 6
-#endif
-// budgeted cylinders of the small instantiation: its cylinder loops (phase 1,
-// chord_parallel in the cylinder-plane fast loop) run over one, and its LDS
-// layout holds 17 rows instead of 25 (no VGPR spills left in it)
-#ifndef SR_NC_SMALL  // round 6: 0 (no budgeted cylinder needs the direction tests, precompute.cpp SR_CYL_DIRFREE)
-#define SR_NC_SMALL 0
-#endif
 #ifndef SR_GENERAL_WAVES_PER_EU
 #define SR_GENERAL_WAVES_PER_EU 5
 #endif
-// the general instantiation: 8 slots, 3 cylinders (25 LDS rows); scenes with
-// more budget slots run the large one (every object budgeted: SR_MAX_BUDGET
-// slots; 29 rows, 7.5 KiB of LDS per wave since round 6: 21 waves per CU)
-#define SR_NB_GENERAL 8
-#define SR_NC_GENERAL SR_NC_KERNEL
 // the large instantiation at 5 waves per SIMD since round 6 (96 VGPRs, no
 // spills, 7.5 KiB of LDS per wave once the cylinder rows went: the stress
 // scene 1.832 -> 1.647 ms per frame, profiles/r06/s45/stress)
@@ -3359,15 +3332,14 @@ __global__ __launch_bounds__(64) void sr_start_table_seq_kernel(const sr_dev_sce
 // the tile's cost (max steps of its rays over the batch).
 // WCOST: the sr_wave_costs instantiation (per-wave steps and events to
 // fr.wave_cost); the frame kernels carry none of its code.
-// NB: budget slots the event path handles (>= the scene's sc->num_budget;
-// sr_launch_geodesic picks SR_NB_SMALL when it suffices: the default scene
-// has six, and phase 1 of an event runs over every slot of the capacity).
-// NC: budgeted cylinders it handles (SR_NC_SMALL with SR_NB_SMALL).
+// NB: budget slots the event path handles (>= the scene's sc->num_budget).
+// NC: budgeted cylinders it handles.
 // TR: the test-ray instantiation (the test ray budgeted, clearance_tr)
-// PROJ: the projection (init_pixel); the angular ones have instantiations of
-// their own (sr_launch_projected), the rectilinear ones are untouched by them
+// PROJ: the projection (init_pixel); the rectilinear instantiations are
+// untouched by the angular ones
 // SEQ: a sequence launch's instantiation (sr_launch_geodesic_seq): sc is an
 // array, frame f reads sc[f]
+// dispatch.h lists the instantiations and says which launch runs which.
 template <bool CULL, bool WCOST = false, int NB = SR_MAX_BUDGET, int FU = SR_FAST_UNROLL, int NC = SR_NC_KERNEL,
           bool TR = false, int PROJ = SR_PROJECTION_RECTILINEAR, bool SEQ = false>
 __global__ __launch_bounds__(SR_WG, sr_integrate_waves(NB, NC)) void sr_integrate_kernel(
@@ -3704,184 +3676,147 @@ __global__ __launch_bounds__(SR_WG) void sr_resume_kernel(const sr_dev_scene* __
     }
 }
 
-// The integrate launch of an angular projection (sr.h "Projections"): four
-// instantiations per projection, each the widest of its kind, so that every
-// scene, the overlay (tested per chord, TR = false, as in the wave-cost
-// launches), culling off, the sparse launch and split tiles are covered:
-//   wave costs              all slots, as sr_launch_geodesic's own
-//   culling off             the reference's loop
-//   the small scene         SR_NB_SMALL slots (the default scene's)
-//   everything else         all slots
-// The latency mode's unroll is not instantiated: such a launch runs the
-// default unroll, with the same pixels (sr.h).
-template <int PROJ>
-static void launch_projected(bool wcost, bool cull, bool small, dim3 grid, hipStream_t stream, const sr_dev_scene* sc,
-                             const float4* tbl, const float* segs, const uint32_t* arr, const uint8_t* opq,
-                             const sr_dev_frame& fr, float* ps, size_t ps_n, int* count, int* order, int* cost,
-                             sr_dev_start* start) {
-    const auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost,
-                           start);
-    };
-    if (wcost)
-        go(sr_integrate_kernel<true, true, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ>);
-    else if (!cull)
-        go(sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1, false, PROJ>);
-    else if (small)
-        go(sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, false, PROJ>);
-    else
-        go(sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ>);
-}
-
 #ifndef SR_RESUME_TILES  // the resume kernel's grid-stride grid, in 256-thread tiles
 #define SR_RESUME_TILES 1024u
 #endif
-// (defined below sr_launch_geodesic: the resume kernels are instantiated after
-// the integrate and shade kernels, as the code object lists them)
-static void launch_resume(bool tr, bool cull, unsigned tiles, hipStream_t stream, const sr_dev_scene* sc,
-                          const float4* tbl, const float* segs, const uint32_t* bg, const uint32_t* arr,
-                          const sr_dev_frame& fr, float* ps, size_t ps_n, uint8_t* out, size_t pitch, float* dbg_rgba,
-                          int32_t* dbg_steps, int* list, int* count);
 
-// order/cost (optional, one int per workgroup tile): the launch order and
-// the cost feedback of order_tiles. order without cost is a sparse launch
-// (sr_render_adaptive): one frame, `order` a caller-made list of whole-tile
-// codes with -1 behind them, one entry per tile of the grid. Only the listed
-// tiles are integrated and shaded, no cost is recorded and no order is
-// computed (order_tiles does not run), split tiles do not apply.
+// ---- the launch path: dispatch.h says which kind of each kernel a launch
+// runs and which launches are refused
+namespace {
+
+// What a launcher passes on. order/cost (optional, one int per workgroup
+// tile): the launch order and the cost feedback of order_tiles; order alone
+// is a sparse launch (dispatch.h sr_launch_plan). xtab: a sequence launch's
+// (sc is then an array). ev4 (optional): four events around the three parts.
+struct Launch {
+    const sr_dev_scene* sc;
+    const float* xtab;
+    const float4* tbl;
+    const float* segs;
+    const uint32_t *bg, *arr;
+    const uint8_t* opq;
+    const sr_dev_frame* fr;
+    uint8_t* out;
+    size_t pitch;
+    float* dbg_rgba;
+    int32_t* dbg_steps;
+    float* ps;
+    size_t ps_n;
+    int *list, *count, *order, *cost, *diag;
+    sr_dev_start* start;
+    hipEvent_t* ev4;
+    hipStream_t stream;
+    sr_launch_plan plan(sr_launch_type type) const {
+        return sr_plan_launch(type, *fr, sr_launch_ptrs{sc, xtab, ps, list, count, order, cost, diag, start, ps_n});
+    }
+};
+
+// The kernel of a kind (each list of dispatch.h expanded, once), nullptr for
+// one that is not instantiated: tests/cpp/test_dispatch.cpp holds that no
+// launch selects one. SEQ: the half of the list to look in, a template
+// argument because a kernel is emitted where its first use is instantiated:
+// the sequence launch's kernels stay behind sr_pick_kernel in the code object.
+template <bool SEQ>
+decltype(&sr_integrate_kernel<true>) integrate_kernel(const sr_integrate_kind& k) {
+#define SR_X(cull, wcost, nb, fu, nc, tr, proj, seq) \
+    if constexpr (seq == SEQ)                        \
+        if (k == sr_integrate_kind{cull, wcost, nb, fu, nc, tr, proj, seq}) return sr_integrate_kernel<cull, wcost, nb, fu, nc, tr, proj, seq>;
+    SR_INTEGRATE_KINDS(SR_X)
+#undef SR_X
+    return nullptr;
+}
+template <bool SEQ>
+decltype(&sr_shade_kernel<false>) shade_kernel(const sr_shade_kind& k) {
+#define SR_X(sparse, seq) \
+    if constexpr (seq == SEQ) if (k == sr_shade_kind{sparse, seq}) return sr_shade_kernel<sparse, seq>;
+    SR_SHADE_KINDS(SR_X)
+#undef SR_X
+    return nullptr;
+}
+template <bool SEQ>
+decltype(&sr_resume_kernel<true>) resume_kernel(const sr_resume_kind& k) {
+#define SR_X(cull, tr, seq) \
+    if constexpr (seq == SEQ) if (k == sr_resume_kind{cull, tr, seq}) return sr_resume_kernel<cull, tr, seq>;
+    SR_RESUME_KINDS(SR_X)
+#undef SR_X
+    return nullptr;
+}
+
+// The second half of a launch, and all of a reshade: the shade kernel (with
+// the next frame's order in its first grid row when there is one to compute)
+// and the resume kernel over the pixel state an integrate kernel wrote.
+template <bool SEQ>
+hipError_t launch_shade_resume(const Launch& L, const sr_launch_plan& p) {
+    const sr_dev_frame& fr = *L.fr;
+    const auto shade = shade_kernel<SEQ>(sr_select_shade(SEQ, p.sparse));
+    const auto resume = resume_kernel<SEQ>(sr_select_resume(fr, SEQ));
+    if (!shade || !resume) return hipErrorInvalidValue;
+    const unsigned B = (unsigned)fr.batch;
+    const OrderArgs oa{L.cost, p.sparse ? nullptr : L.order, (int)p.tiles, fr.max_steps, p.split, p.split_log2,
+                       fr.split_min_steps};
+    hipLaunchKernelGGL(shade, dim3(p.gx, p.gy * B + (oa.order ? 1u : 0u)), dim3(256), 0, L.stream, L.sc, L.segs, L.bg, L.arr,
+                       fr, L.ps, L.ps_n, L.out, L.pitch, L.dbg_rgba, L.dbg_steps, L.list, L.count, L.diag, oa,
+                       p.sparse ? (const int*)L.order : nullptr);
+    if (L.ev4) (void)hipEventRecord(L.ev4[2], L.stream);
+    const unsigned tiles = p.tiles * B < SR_RESUME_TILES ? p.tiles * B : SR_RESUME_TILES;  // a grid-stride grid
+    hipLaunchKernelGGL(resume, dim3(tiles * SR_WG_PER_TILE), dim3(SR_WG), 0,
+                       L.stream, L.sc, L.tbl, L.segs, L.bg, L.arr, fr, L.ps, L.ps_n, L.out, L.pitch, L.dbg_rgba, L.dbg_steps,
+                       L.list, L.count);
+    if (L.ev4) (void)hipEventRecord(L.ev4[3], L.stream);
+    return hipGetLastError();
+}
+
+// A frame launch or (SEQ) a sequence launch: the frames' start records, on
+// every launch (the cameras, the scene and the schedule are the launch's own;
+// the integrate time includes it), the integrate kernel, then the half above.
+template <bool SEQ>
+hipError_t launch_frames(const Launch& L) {
+    const sr_dev_frame& fr = *L.fr;
+    const sr_launch_plan p = L.plan(SEQ ? SR_LAUNCH_SEQ : SR_LAUNCH_FRAME);
+    if (p.verdict != SR_LAUNCH_GO) return p.verdict == SR_LAUNCH_EMPTY ? hipSuccess : hipErrorInvalidValue;
+    const auto integrate = integrate_kernel<SEQ>(sr_select_integrate(fr, SEQ));
+    if (!integrate) return hipErrorInvalidValue;
+    const unsigned B = (unsigned)fr.batch;
+    if (L.ev4) (void)hipEventRecord(L.ev4[0], L.stream);
+    if constexpr (SEQ)
+        hipLaunchKernelGGL(sr_start_table_seq_kernel, dim3(B), dim3(1), 0, L.stream, L.sc, L.segs, fr, L.start, L.xtab);
+    else
+        hipLaunchKernelGGL(sr_start_table_kernel, dim3(B), dim3(1), 0, L.stream, L.sc, L.segs, fr, L.start);
+    hipLaunchKernelGGL(integrate, dim3(p.slots * B * SR_WG_PER_TILE), dim3(SR_WG), 0, L.stream, L.sc, L.tbl, L.segs, L.arr,
+                       L.opq, fr, L.ps, L.ps_n, L.count, L.order, L.cost, L.start);
+    if (L.ev4) (void)hipEventRecord(L.ev4[1], L.stream);
+    return launch_shade_resume<SEQ>(L, p);
+}
+
+}  // namespace
+
 extern "C" hipError_t sr_launch_geodesic(const sr_dev_scene* sc, const float4* tbl, const float* segs,
                                          const uint32_t* bg, const uint32_t* arr, const uint8_t* opq,
                                          const sr_dev_frame* fr, uint8_t* out, size_t pitch, float* dbg_rgba,
                                          int32_t* dbg_steps, float* ps, size_t ps_n, int* list, int* count,
                                          int* order, int* cost, int* diag, sr_dev_start* start, hipEvent_t* ev4,
                                          hipStream_t stream) {
-    dim3 block(256);
-    dim3 grid((fr->width + 15) / 16, (fr->nrows + 15) / 16);
-    if (grid.x == 0 || grid.y == 0) return hipSuccess;
-    const unsigned nblocks = grid.x * grid.y;
-    const unsigned B = (unsigned)fr->batch;
-    if (B < 1 || B > SR_MAX_BATCH || fr->tiles != (int)nblocks) return hipErrorInvalidValue;
-    if ((size_t)nblocks * B * 256 > ps_n || (size_t)nblocks * B * 256 > (size_t)INT32_MAX) return hipErrorInvalidValue;
-    if (cost != nullptr && order == nullptr) return hipErrorInvalidValue;
-    const bool sparse = order != nullptr && cost == nullptr;
-    if (sparse && (B != 1 || fr->wave_cost)) return hipErrorInvalidValue;
-    // split tiles need the launch order (their codes come from order_tiles)
-    const int split = order && !sparse ? fr->split_tiles : 0;
-    if (split < 0 || (split && (fr->split_log2 < 0 || fr->split_log2 > 4 || (fr->split_log2 & 1))))
-        return hipErrorInvalidValue;
-    if (nblocks > (1u << 22)) return hipErrorInvalidValue;  // tile << 8 stays a positive int
-    if (fr->projection < SR_PROJECTION_RECTILINEAR || fr->projection > SR_PROJECTION_FISHEYE) return hipErrorInvalidValue;
-    const unsigned slots = nblocks + ((64u >> (split ? fr->split_log2 : 6)) - 1u) * (unsigned)split;
-    const bool cull = fr->cull != 0;
-    // the small instantiation (6 slots, 1 cylinder: 17 LDS rows) when the
-    // scene fits it, the general one (8 slots) or the large one (every object)
-    const bool small = cull && fr->num_budget <= SR_NB_SMALL && fr->num_budget_cyl <= SR_NC_SMALL;
-    const bool general = fr->num_budget <= SR_NB_GENERAL;
-    const bool tr = cull && fr->tr_visible != 0;
-    // cylinders with direction tests beyond what the instantiations handle (a
-    // host built with SR_CYL_DIRFREE=0 against a kernel without them)
-    if (cull && fr->num_budget_cyl > SR_NC_KERNEL && !small) return hipErrorInvalidValue;
-    if (!start) return hipErrorInvalidValue;
-    if (ev4) (void)hipEventRecord(ev4[0], stream);
-    // the frames' start records, on every launch (the cameras, the scene and
-    // the schedule are the launch's own; the integrate time includes it)
-    hipLaunchKernelGGL(sr_start_table_kernel, dim3(B), dim3(1), 0, stream, sc, segs, *fr, start);
-    const dim3 igrid(slots * B * SR_WG_PER_TILE);
-    const auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, igrid, dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count, order, cost,
-                           start);
-    };
-    if (fr->projection == SR_PROJECTION_EQUIRECT)
-        launch_projected<SR_PROJECTION_EQUIRECT>(fr->wave_cost != nullptr, cull, small, igrid, stream, sc, tbl, segs, arr,
-                                                 opq, *fr, ps, ps_n, count, order, cost, start);
-    else if (fr->projection == SR_PROJECTION_FISHEYE)
-        launch_projected<SR_PROJECTION_FISHEYE>(fr->wave_cost != nullptr, cull, small, igrid, stream, sc, tbl, segs, arr,
-                                                opq, *fr, ps, ps_n, count, order, cost, start);
-    else if (fr->wave_cost && general)
-        go(sr_integrate_kernel<true, true, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>);
-    else if (fr->wave_cost)
-        go(sr_integrate_kernel<true, true>);
-    else if (small && tr)  // the test-ray instantiations (the overlay visible)
-        go(sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, true>);
-    else if (cull && general && tr)
-        go(sr_integrate_kernel<true, false, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL, true>);
-    else if (cull && tr)
-        go(sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, true>);
-    else if (small && fr->fast_unroll == 2)  // latency mode (sr_set_latency_mode)
-        go(sr_integrate_kernel<true, false, SR_NB_SMALL, 2, SR_NC_SMALL>);
-    else if (small)
-        go(sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL>);
-    else if (cull && general)
-        go(sr_integrate_kernel<true, false, SR_NB_GENERAL, SR_FAST_UNROLL, SR_NC_GENERAL>);
-    else if (cull)
-        go(sr_integrate_kernel<true>);
-    else  // the reference's loop (no budgets: the smallest LDS layout)
-        go(sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1>);
-    if (ev4) (void)hipEventRecord(ev4[1], stream);
-    OrderArgs oa{cost, sparse ? nullptr : order, (int)nblocks, fr->max_steps, split, split ? fr->split_log2 : 6, fr->split_min_steps};
-    if (sparse)
-        hipLaunchKernelGGL(sr_shade_kernel<true>, dim3(grid.x, grid.y), block, 0, stream, sc, segs, bg, arr, *fr, ps, ps_n,
-                           out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa, (const int*)order);
-    else
-        hipLaunchKernelGGL(sr_shade_kernel<false>, dim3(grid.x, grid.y * B + (order ? 1u : 0u)), block, 0, stream, sc,
-                           segs, bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa,
-                           (const int*)nullptr);
-    if (ev4) (void)hipEventRecord(ev4[2], stream);
-    launch_resume(tr, cull, nblocks * B, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list,
-                  count);
-    if (ev4) (void)hipEventRecord(ev4[3], stream);
-    return hipGetLastError();
-}
-
-// The resume kernel of a launch's kind (the test ray budgeted, culling on,
-// the reference's loop) over `tiles` 256-pixel tiles of pixel state.
-static void launch_resume(bool tr, bool cull, unsigned tiles, hipStream_t stream, const sr_dev_scene* sc,
-                          const float4* tbl, const float* segs, const uint32_t* bg, const uint32_t* arr,
-                          const sr_dev_frame& fr, float* ps, size_t ps_n, uint8_t* out, size_t pitch, float* dbg_rgba,
-                          int32_t* dbg_steps, int* list, int* count) {
-    const dim3 grid((tiles < SR_RESUME_TILES ? tiles : SR_RESUME_TILES) * SR_WG_PER_TILE);
-    const auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, fr, ps, ps_n, out, pitch, dbg_rgba,
-                           dbg_steps, list, count);
-    };
-    if (tr)
-        go(sr_resume_kernel<true, true>);
-    else if (cull)
-        go(sr_resume_kernel<true>);
-    else
-        go(sr_resume_kernel<false>);
+    return launch_frames<false>(Launch{sc, nullptr, tbl, segs, bg, arr, opq, fr, out, pitch, dbg_rgba, dbg_steps, ps, ps_n,
+                                       list, count, order, cost, diag, start, ev4, stream});
 }
 
 // ---- retained frames (sr.h): the pixel state a launch left, shaded again or
 // read for the first surface of every ray
 
-// sr_reshade: the shade and resume kernels of sr_launch_geodesic alone, on
-// the pixel state its integrate kernel wrote. The resume counter, which that
-// kernel's first workgroup clears, is cleared on the stream here; the shade
-// kernel runs without an order (order_tiles does not run, no learned order
-// or cost is touched).
+// sr_reshade: the shade and resume kernels of sr_launch_geodesic alone, on the pixel state its integrate
+// kernel wrote. The resume counter, which that kernel's first workgroup clears, is cleared on the stream here;
+// the shade kernel runs without an order (order_tiles does not run, no learned order or cost is touched).
 extern "C" hipError_t sr_launch_reshade(const sr_dev_scene* sc, const float4* tbl, const float* segs,
                                         const uint32_t* bg, const uint32_t* arr, const sr_dev_frame* fr, uint8_t* out,
                                         size_t pitch, float* dbg_rgba, int32_t* dbg_steps, float* ps, size_t ps_n,
                                         int* list, int* count, int* diag, hipStream_t stream) {
-    dim3 block(256);
-    dim3 grid((fr->width + 15) / 16, (fr->nrows + 15) / 16);
-    if (grid.x == 0 || grid.y == 0) return hipSuccess;
-    const unsigned nblocks = grid.x * grid.y;
-    const unsigned B = (unsigned)fr->batch;
-    if (B < 1 || B > SR_MAX_BATCH || fr->tiles != (int)nblocks) return hipErrorInvalidValue;
-    if ((size_t)nblocks * B * 256 > ps_n || (size_t)nblocks * B * 256 > (size_t)INT32_MAX) return hipErrorInvalidValue;
-    if (!ps || !list || !count || !diag || fr->wave_cost) return hipErrorInvalidValue;
-    const bool cull = fr->cull != 0;
-    const bool tr = cull && fr->tr_visible != 0;
+    const Launch L{sc, /*xtab*/ nullptr, tbl, segs, bg, arr, /*opq*/ nullptr, fr, out, pitch, dbg_rgba, dbg_steps, ps, ps_n,
+                   list, count, /*order*/ nullptr, /*cost*/ nullptr, diag, /*start*/ nullptr, /*ev4*/ nullptr, stream};
+    const sr_launch_plan p = L.plan(SR_LAUNCH_RESHADE);
+    if (p.verdict != SR_LAUNCH_GO) return p.verdict == SR_LAUNCH_EMPTY ? hipSuccess : hipErrorInvalidValue;
     const hipError_t e = hipMemsetAsync(count, 0, sizeof(int), stream);
     if (e != hipSuccess) return e;
-    OrderArgs oa{nullptr, nullptr, (int)nblocks, fr->max_steps, 0, 6, fr->split_min_steps};
-    hipLaunchKernelGGL(sr_shade_kernel<false>, dim3(grid.x, grid.y * B), block, 0, stream, sc, segs, bg, arr, *fr, ps,
-                       ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa, (const int*)nullptr);
-    launch_resume(tr, cull, nblocks * B, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list,
-                  count);
-    return hipGetLastError();
+    return launch_shade_resume<false>(L, p);
 }
 
 // sr_pick_map's codes (sr.h SR_PICK_*) for the slots of a Hit
@@ -3963,89 +3898,16 @@ extern "C" hipError_t sr_launch_pick(const sr_dev_scene* sc, const float* segs, 
 
 // ---- scene sequences (sr.h): one launch whose frame f reads the scene sc[f]
 
-// The sequence integrate kernel of a launch's kind, three per projection:
-// culling off (the reference's loop), the small layout (every scene of the
-// window fits SR_NB_SMALL slots and SR_NC_SMALL cylinders: fr.num_budget and
-// fr.num_budget_cyl are the window's maxima) and all slots. The overlay is
-// tested per chord (TR = false, as in the projected launches); the latency
-// mode's unroll is not instantiated (the default unroll, the same pixels).
-template <int PROJ>
-static void launch_integrate_seq(bool cull, bool small, dim3 grid, hipStream_t stream, const sr_dev_scene* sc,
-                                 const float4* tbl, const float* segs, const uint32_t* arr, const uint8_t* opq,
-                                 const sr_dev_frame& fr, float* ps, size_t ps_n, int* count, int* order, int* cost,
-                                 sr_dev_start* start) {
-    const auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(SR_WG), 0, stream, sc, tbl, segs, arr, opq, fr, ps, ps_n, count, order, cost,
-                           start);
-    };
-    if (!cull)
-        go(sr_integrate_kernel<false, false, 1, SR_FAST_UNROLL, 1, false, PROJ, true>);
-    else if (small)
-        go(sr_integrate_kernel<true, false, SR_NB_SMALL, SR_FAST_UNROLL, SR_NC_SMALL, false, PROJ, true>);
-    else
-        go(sr_integrate_kernel<true, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, false, PROJ, true>);
-}
-
-// sr_launch_geodesic for the frames of a scene sequence: sc[f] is frame f's
-// scene (fr->batch of them), xtab their low-energy exclusions for the launch's
-// (u_f, step angle), SR_XTAB_FLOATS floats per scene. fr->num_budget and
-// fr->num_budget_cyl are the maxima over sc[0 .. batch), fr's own exclusions
-// "none". No sparse launch, no wave costs.
+// sr_launch_geodesic for the frames of a scene sequence (launchers.h; xtab for the launch's (u_f, step angle)).
+// fr->num_budget and fr->num_budget_cyl are the maxima over sc[0 .. batch), fr's own exclusions "none".
 extern "C" hipError_t sr_launch_geodesic_seq(const sr_dev_scene* sc, const float* xtab, const float4* tbl,
                                              const float* segs, const uint32_t* bg, const uint32_t* arr,
                                              const uint8_t* opq, const sr_dev_frame* fr, uint8_t* out, size_t pitch,
                                              float* dbg_rgba, int32_t* dbg_steps, float* ps, size_t ps_n, int* list,
                                              int* count, int* order, int* cost, int* diag, sr_dev_start* start,
                                              hipEvent_t* ev4, hipStream_t stream) {
-    dim3 block(256);
-    dim3 grid((fr->width + 15) / 16, (fr->nrows + 15) / 16);
-    if (grid.x == 0 || grid.y == 0) return hipSuccess;
-    const unsigned nblocks = grid.x * grid.y;
-    const unsigned B = (unsigned)fr->batch;
-    if (B < 1 || B > SR_MAX_BATCH || fr->tiles != (int)nblocks) return hipErrorInvalidValue;
-    if ((size_t)nblocks * B * 256 > ps_n || (size_t)nblocks * B * 256 > (size_t)INT32_MAX) return hipErrorInvalidValue;
-    if ((cost == nullptr) != (order == nullptr) || fr->wave_cost) return hipErrorInvalidValue;
-    const int split = order ? fr->split_tiles : 0;
-    if (split < 0 || (split && (fr->split_log2 < 0 || fr->split_log2 > 4 || (fr->split_log2 & 1))))
-        return hipErrorInvalidValue;
-    if (nblocks > (1u << 22)) return hipErrorInvalidValue;  // tile << 8 stays a positive int
-    if (fr->projection < SR_PROJECTION_RECTILINEAR || fr->projection > SR_PROJECTION_FISHEYE) return hipErrorInvalidValue;
-    const unsigned slots = nblocks + ((64u >> (split ? fr->split_log2 : 6)) - 1u) * (unsigned)split;
-    const bool cull = fr->cull != 0;
-    const bool small = cull && fr->num_budget <= SR_NB_SMALL && fr->num_budget_cyl <= SR_NC_SMALL;
-    if (cull && fr->num_budget_cyl > SR_NC_KERNEL && !small) return hipErrorInvalidValue;
-    if (!sc || !xtab || !start) return hipErrorInvalidValue;
-    if (ev4) (void)hipEventRecord(ev4[0], stream);
-    hipLaunchKernelGGL(sr_start_table_seq_kernel, dim3(B), dim3(1), 0, stream, sc, segs, *fr, start, xtab);
-    const dim3 igrid(slots * B * SR_WG_PER_TILE);
-    if (fr->projection == SR_PROJECTION_EQUIRECT)
-        launch_integrate_seq<SR_PROJECTION_EQUIRECT>(cull, small, igrid, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count,
-                                                     order, cost, start);
-    else if (fr->projection == SR_PROJECTION_FISHEYE)
-        launch_integrate_seq<SR_PROJECTION_FISHEYE>(cull, small, igrid, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n, count,
-                                                    order, cost, start);
-    else
-        launch_integrate_seq<SR_PROJECTION_RECTILINEAR>(cull, small, igrid, stream, sc, tbl, segs, arr, opq, *fr, ps, ps_n,
-                                                        count, order, cost, start);
-    if (ev4) (void)hipEventRecord(ev4[1], stream);
-    OrderArgs oa{cost, order, (int)nblocks, fr->max_steps, split, split ? fr->split_log2 : 6, fr->split_min_steps};
-    hipLaunchKernelGGL((sr_shade_kernel<false, true>), dim3(grid.x, grid.y * B + (order ? 1u : 0u)), block, 0, stream, sc, segs,
-                       bg, arr, *fr, ps, ps_n, out, pitch, dbg_rgba, dbg_steps, list, count, diag, oa, (const int*)nullptr);
-    if (ev4) (void)hipEventRecord(ev4[2], stream);
-    {
-        const unsigned tiles = nblocks * B;
-        const dim3 rgrid((tiles < SR_RESUME_TILES ? tiles : SR_RESUME_TILES) * SR_WG_PER_TILE);
-        const auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, rgrid, dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, ps, ps_n, out, pitch,
-                               dbg_rgba, dbg_steps, list, count);
-        };
-        if (cull)
-            go(sr_resume_kernel<true, false, true>);
-        else
-            go(sr_resume_kernel<false, false, true>);
-    }
-    if (ev4) (void)hipEventRecord(ev4[3], stream);
-    return hipGetLastError();
+    return launch_frames<true>(Launch{sc, xtab, tbl, segs, bg, arr, opq, fr, out, pitch, dbg_rgba, dbg_steps, ps, ps_n, list,
+                                      count, order, cost, diag, start, ev4, stream});
 }
 
 // ---- ray queries (sr.h "Ray queries"): caller-supplied rays, one lane each
@@ -4151,25 +4013,18 @@ extern "C" hipError_t sr_launch_trace(const sr_dev_scene* sc, const float4* tbl,
                                       const uint32_t* arr, const sr_dev_frame* fr, const float* origins,
                                       const float* dirs, int n_rays, float* out_rgba, uint8_t* out_rgba8,
                                       int32_t* out_steps, int32_t* out_ids, hipStream_t stream) {
-    if (n_rays < 0 || n_rays > SR_TRACE_MAX_RAYS) return hipErrorInvalidValue;
-    if (n_rays == 0) return hipSuccess;
-    if (!sc || !tbl || !fr || !origins || !dirs || (!out_rgba && !out_rgba8 && !out_steps && !out_ids))
-        return hipErrorInvalidValue;
-    const bool cull = fr->cull != 0;
-    const bool tr = cull && fr->tr_visible != 0;
-    // cylinders with direction tests beyond what the instantiation handles (sr_launch_geodesic)
-    if (cull && fr->num_budget_cyl > SR_NC_KERNEL) return hipErrorInvalidValue;
+    const sr_verdict v = sr_check_trace(fr, n_rays, sc && tbl && origins && dirs, out_rgba || out_rgba8 || out_steps || out_ids);
+    if (v != SR_LAUNCH_GO) return v == SR_LAUNCH_EMPTY ? hipSuccess : hipErrorInvalidValue;
+    const sr_trace_kind k = sr_select_trace(*fr);
+    decltype(&sr_trace_kernel<true>) kernel = nullptr;
+#define SR_X(cull, tr) \
+    if (k == sr_trace_kind{cull, tr}) kernel = sr_trace_kernel<cull, tr>;
+    SR_TRACE_KINDS(SR_X)
+#undef SR_X
+    if (!kernel) return hipErrorInvalidValue;
     const unsigned groups = ((unsigned)n_rays + SR_WG - 1u) / SR_WG;
-    const dim3 grid(groups < SR_TRACE_GROUPS ? groups : SR_TRACE_GROUPS);
-    const auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, dim3(SR_WG), 0, stream, sc, tbl, segs, bg, arr, *fr, origins, dirs, n_rays,
-                           out_rgba, reinterpret_cast<uint32_t*>(out_rgba8), out_steps, out_ids);
-    };
-    if (tr)  // the overlay budgeted, as the resume kernel's
-        go(sr_trace_kernel<true, true>);
-    else if (cull)
-        go(sr_trace_kernel<true>);
-    else  // the reference's loop
-        go(sr_trace_kernel<false>);
+    hipLaunchKernelGGL(kernel, dim3(groups < SR_TRACE_GROUPS ? groups : SR_TRACE_GROUPS), dim3(SR_WG), 0, stream, sc, tbl,
+                       segs, bg, arr, *fr, origins, dirs, n_rays, out_rgba, reinterpret_cast<uint32_t*>(out_rgba8), out_steps,
+                       out_ids);
     return hipGetLastError();
 }

@@ -1,9 +1,10 @@
 """Every launch path on every kernel instantiation, at partial waves.
 
 sr_launch_geodesic dispatches ten sr_integrate_kernel and three
-sr_resume_kernel instantiations (small / general / large budget layouts,
-their test-ray variants, the 2-step latency loop, the two sr_wave_costs
-ones, the cull-off loop). tests/test_gpu_parity.py runs the launch paths on
+sr_resume_kernel instantiations of the pinhole projection:
+csrc/kernels/dispatch.h lists them and says which launch runs which, and
+tests/test_dispatch.py holds that rule on the CPU (no pixel depends on it,
+so nothing here can see it). tests/test_gpu_parity.py runs the launch paths on
 the default scene (the small instantiation) and the other instantiations
 through whole render_debug frames; this module runs the cross product on a
 frame whose every wave shape is partial somewhere, plus the frame shapes,
