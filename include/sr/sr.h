@@ -774,9 +774,10 @@ int sr_projection_dir(int projection, float fov, int uv_width, int uv_height, in
  * A sequence launch leaves no retained frame ("the context's current scene"
  * has no meaning for it): sr_can_reshade is 0, and sr_reshade,
  * sr_reshade_debug and sr_pick_map return SR_E_NOT_READY until the next plain
- * launch. Sample phases, sr_render_adaptive and sr_wave_costs have no
- * sequence form; to price a rank's block lists use sr_set_scene with one
- * scene of the sequence. */
+ * launch. Sample phases have their sequence form in "Shutter frames" below
+ * (sr_render_phase and sr_render_accumulate themselves render the context's
+ * own scene); sr_render_adaptive and sr_wave_costs have no sequence form: to
+ * price a rank's block lists use sr_set_scene with one scene of the sequence. */
 #define SR_MAX_SEQUENCE 256
 /* Snapshot copies of n scenes (1 .. SR_MAX_SEQUENCE), each validated and
  * packed as sr_set_scene does with the context's current test ray, uploaded
@@ -809,6 +810,108 @@ int sr_render_sequence_block_list(sr_ctx* ctx, int first_scene, const sr_camera*
 int sr_render_sequence_debug(sr_ctx* ctx, int scene_index, const sr_camera* cam, const sr_params* params,
                              int width, int height, int row_begin, int row_end, float* dev_rgba32,
                              uint8_t* dev_rgba8, int32_t* dev_steps, sr_stream stream);
+
+/* ---- Shutter frames (not in the reference, whose every frame is an
+ * instantaneous snapshot). Time-distributed sampling: output frame m is the
+ * mean of K sub-frames, each with its own scene of the sequence, its own
+ * camera and its own sub-pixel phase, all M * K of them rendered by ONE
+ * batched launch. With K = ss * ss and the progressive phase order, motion
+ * blur comes at the price of anti-aliasing alone.
+ *
+ * Inputs: K = sub_frames >= 1 and M = n_frames >= 1 with M * K <=
+ * SR_MAX_BATCH (32); ss in 1 .. SR_MAX_SUPERSAMPLE; cams[M * K]; phases:
+ * M * K byte pairs {x, y}, each < ss (host memory, read during the call), or
+ * NULL for pair j = sr_phase_order(ss, (j mod K) mod (ss * ss)); first_scene.
+ *
+ * Definition. Sub-frame j = m * K + k (k < K) is the phase image
+ * phase(phases[j]), exactly as "Sample phases" defines it, of the sample
+ * frame S_j: the frame this library renders at (ss * width) x (ss * height)
+ * for cams[j] with the call's params and the context's textures, test ray,
+ * projection and settings. Its scene is scene first_scene + j of the
+ * context's sequence, or the context's own scene (sr_set_scene) for every j
+ * when first_scene == SR_SHUTTER_OWN_SCENE. Output frame m, every channel
+ * alike, in integers:
+ *
+ *   out_m[y][x][c] = min(255, (sum_{k < K} sub_{m K + k}[y][x][c] + K / 2) div K)
+ *
+ * which is sr_accum_resolve's rule with n = K. Hence
+ *  - K == 1, ss == 1 is sr_render_sequence (own scene: sr_render_blocks_batch)
+ *    byte for byte;
+ *  - K == ss * ss with one scene, one camera and the default phases is
+ *    sr_render_ss byte for byte;
+ *  - one scene and one camera with any phases equals sr_render_accumulate and
+ *    sr_accum_resolve;
+ *  - the crosshair, the noise mask (percent_black) and the split modes
+ *    (raytrace_type) are evaluated per sub-frame sample, as in S_j.
+ * Layout, pitch, frame stride, the block list's -1 padding and the rows left
+ * unwritten are those of sr_render_sequence(_block_list) for M frames; the
+ * output pointer, pitch and frame stride must be multiples of 4. The call is
+ * asynchronous on `stream` with no host wait. The sub-frames have the grid,
+ * the pixel state and the launch order of a plain width x rows batch of M * K
+ * frames: the order cached for that shape is learned and used as a batch
+ * does; split tiles, culling and the projection apply, and the latency mode
+ * as for the underlying launch kind (the default unroll under a sequence).
+ * Scratch: the context's sample buffer, 4 * width * rows * M * K bytes, and
+ * the pixel state of M * K plain frames (208 bytes per pixel): the memory of
+ * M * K plain frames, not of a sample frame per sub-frame.
+ *
+ * A shutter call leaves no retained frame (sr_can_reshade is 0; sr_reshade,
+ * sr_reshade_debug and sr_pick_map return SR_E_NOT_READY until the next plain
+ * launch) and touches neither the sequence nor the context's own scene.
+ *
+ * Rejections, all before anything is launched and with nothing written:
+ * SR_E_INVALID for K < 1, M < 1, null pointers, ss out of range, a phase
+ * coordinate >= ss, first_scene < -1, a window [first_scene, first_scene +
+ * M * K) that leaves the sequence, and the band, pitch, stride, block-list or
+ * accumulator errors of sr_render_sequence(_block_list) and
+ * sr_render_accumulate; SR_E_CAPACITY for M * K > 32; SR_E_NOT_READY without
+ * a sequence, or (own scene) without sr_set_scene; SR_E_NOMEM as for
+ * sr_render_accumulate. Shutter forms of sr_render_adaptive, sr_wave_costs,
+ * sr_trace_rays and retained frames do not exist; a shutter is a box (every
+ * sub-frame weighs the same) over consecutive scenes. */
+#define SR_SHUTTER_OWN_SCENE (-1)
+/* Rows [row_begin, row_end) of n_frames shutter frames, frame m at dev_rgba8 +
+ * m * frame_stride_bytes. */
+int sr_render_shutter(sr_ctx* ctx, int first_scene, const sr_camera* cams, const uint8_t* phases, int sub_frames,
+                      int n_frames, const sr_params* params, int width, int height, int row_begin, int row_end,
+                      int ss, uint8_t* dev_rgba8, size_t pitch_bytes, size_t frame_stride_bytes, sr_stream stream);
+/* The same for the blocks of a list (-1: padding, its rows unwritten): a
+ * rank's share in the shape sr_assemble_blocks expects, as
+ * sr_render_sequence_block_list. Price the lists with sr_wave_costs on one
+ * sub-frame's scene. */
+int sr_render_shutter_block_list(sr_ctx* ctx, int first_scene, const sr_camera* cams, const uint8_t* phases,
+                                 int sub_frames, int n_frames, const sr_params* params, int width, int height,
+                                 int block_rows, const int* blocks, int n_blocks, int ss, uint8_t* dev_rgba8,
+                                 size_t pitch_bytes, size_t frame_stride_bytes, sr_stream stream);
+/* sr_render_accumulate with a camera and a scene per sub-frame: the n_sub
+ * (1 .. 32) sub-frames j of ONE group (cams[j], phases[j] or the default
+ * pair of j, scene first_scene + j or the own scene) in one launch, added to
+ * the accumulator's rows [0, row_end - row_begin), or stored when reset != 0.
+ * Shutters longer than 32 sub-frames (up to SR_MAX_ACCUM_PASSES) take several
+ * calls, and any prefix is a displayable frame; resolve with sr_accum_resolve
+ * and the number of sub-frames added. Any grouping of a frame's sub-frames
+ * resolves to sr_render_shutter's frame, byte for byte. */
+int sr_render_accumulate_shutter(sr_ctx* ctx, int first_scene, const sr_camera* cams, const uint8_t* phases,
+                                 int n_sub, const sr_params* params, int width, int height, int row_begin,
+                                 int row_end, int ss, int reset, uint16_t* dev_accum, size_t accum_pitch_bytes,
+                                 sr_stream stream);
+/* The group resolve alone, by the rule above: n_frames * sub_frames RGBA8
+ * images of width x rows (row r of image j at images + j * image_stride +
+ * r * pitch) to n_frames frames, frame m from images m * sub_frames ..
+ * (m + 1) * sub_frames - 1, at out + m * out_frame_stride. sub_frames in
+ * 1 .. SR_MAX_ACCUM_PASSES, n_frames in 1 .. 65535; pointers, pitches and
+ * strides multiples of 4 (multiples of 16 run the kernel's vector path).
+ * on_device != 0: device pointers, a kernel on `stream`, asynchronous; 0:
+ * host memory, synchronous (the same rule in plain C++). SR_E_INVALID for
+ * null pointers, sizes <= 0, a short pitch or stride, a misaligned pointer,
+ * pitch or stride, or a count out of range. */
+int sr_shutter_resolve(const uint8_t* images, size_t pitch, size_t image_stride, int sub_frames, int n_frames,
+                       int width, int rows, uint8_t* out, size_t out_pitch, size_t out_frame_stride, int on_device,
+                       sr_stream stream);
+/* The default phases (host only): out_pairs[2 k], out_pairs[2 k + 1] =
+ * sr_phase_order(ss, k mod (ss * ss)) for k < sub_frames. SR_E_INVALID for ss
+ * out of range, sub_frames < 1 or a null pointer. */
+int sr_shutter_phases(int ss, int sub_frames, uint8_t* out_pairs);
 
 /* ---- Ray queries (not in the reference, whose every ray starts at the one
  * camera position). A trace launch walks rays the caller supplies, each with

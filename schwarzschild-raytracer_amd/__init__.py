@@ -7,6 +7,7 @@ Layout:
   csrc/sr_api.cpp            the C-ABI of include/sr/sr.h: context, uploads, dispatch
   csrc/host/precompute.cpp   the host arithmetic behind the culling margins (no HIP)
   csrc/kernels/launchers.h   the kernel files' host entries, declared once
+  csrc/kernels/shutter.hip   the group resolve of shutter frames (beside resolve, accum, adaptive, assemble)
   csrc/host/scene.cpp        the reference-shaped C++ scene model (include/sr/scene.hpp)
   abi.py                     ctypes mirror of sr.h
   renderer.py                Renderer: device handle (torch for memory/streams)
@@ -18,8 +19,9 @@ Import as a package via `load_package()` in bench.py / tests (the directory
 name is not a Python identifier).
 """
 from . import abi, assets, dist, scenes  # noqa: F401
+from .abi import shutter_phases, shutter_resolve  # noqa: F401  (host forms; Renderer.shutter_resolve: the device's)
 
-__all__ = ["abi", "assets", "dist", "scenes", "Renderer", "camera_rays"]
+__all__ = ["abi", "assets", "dist", "scenes", "Renderer", "camera_rays", "shutter_phases", "shutter_resolve"]
 
 
 def __getattr__(name):

@@ -232,6 +232,14 @@ SIGNATURES = {
     "sr_render_sequence_debug": (_i, [_p, _i, C.POINTER(Camera), C.POINTER(Params), _i, _i, _i, _i, _p, _p, _p, _p]),
     "sr_trace_rays": (_i, [_p, _p, _p, _i, C.POINTER(Params), _p, _p, _p, _p, _p]),
     "sr_camera_rays": (_i, [C.POINTER(Camera), _i, _i, _i, _i, _i, _p, _p]),
+    "sr_render_shutter": (_i, [_p, _i, C.POINTER(Camera), _p, _i, _i, C.POINTER(Params), _i, _i, _i, _i, _i, _p,
+                               C.c_size_t, C.c_size_t, _p]),
+    "sr_render_shutter_block_list": (_i, [_p, _i, C.POINTER(Camera), _p, _i, _i, C.POINTER(Params), _i, _i, _i,
+                                          C.POINTER(_i), _i, _i, _p, C.c_size_t, C.c_size_t, _p]),
+    "sr_render_accumulate_shutter": (_i, [_p, _i, C.POINTER(Camera), _p, _i, C.POINTER(Params), _i, _i, _i, _i, _i, _i,
+                                          _p, C.c_size_t, _p]),
+    "sr_shutter_resolve": (_i, [_p, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _p, C.c_size_t, C.c_size_t, _i, _p]),
+    "sr_shutter_phases": (_i, [_i, _i, _p]),
 }
 # sr_set_projection's values (sr.h "Projections")
 PROJECTION_RECTILINEAR, PROJECTION_EQUIRECT, PROJECTION_FISHEYE = 0, 1, 2
@@ -242,6 +250,9 @@ SINCE_PROJECTIONS = ("sr_set_projection", "sr_get_projection", "sr_projection_di
 SINCE_SEQUENCES = ("sr_set_scene_sequence", "sr_scene_sequence_length", "sr_render_sequence",
                    "sr_render_sequence_block_list", "sr_render_sequence_debug")
 SINCE_TRACE = ("sr_trace_rays", "sr_camera_rays")
+SINCE_SHUTTER = ("sr_render_shutter", "sr_render_shutter_block_list", "sr_render_accumulate_shutter",
+                 "sr_shutter_resolve", "sr_shutter_phases")
+SHUTTER_OWN_SCENE = -1  # sr_render_shutter's first_scene for the context's own scene (sr.h "Shutter frames")
 TRACE_MAX_RAYS = 1 << 28  # rays of one trace launch (sr.h "Ray queries")
 MAX_SEQUENCE = 256  # scenes of a sequence (sr.h "Scene sequences")
 # sr_pick_map's codes below the indices into scene.objects[]
@@ -264,6 +275,7 @@ EXTRA_SIGNATURES = {
                             _i, _p]),
     "sr_debug_step_table": (_i, [_i, _i, _p, C.c_size_t]),
     "sr_debug_opacity_bits": (_i, [_p, _i, _i, _i, _i, _p, C.c_size_t]),
+    "sr_debug_shutter_div": (_i, [_i, _i]),
 }
 
 _lib = None
@@ -290,7 +302,7 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
     lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **EXTRA_SIGNATURES}.items():
         if (name in EXTRA_SIGNATURES or name in SINCE_PROJECTIONS or name in SINCE_SEQUENCES or
-                name in SINCE_TRACE) and not hasattr(lib, name):
+                name in SINCE_TRACE or name in SINCE_SHUTTER) and not hasattr(lib, name):
             continue  # debug tooling and newer calls an older library (a bisection build) may lack
         fn = getattr(lib, name)
         fn.restype = res
@@ -446,6 +458,35 @@ def accum_resolve(accum, n: int):
     if rows and w:
         check(load().sr_accum_resolve(a.ctypes.data, a.strides[0], w, rows, int(n), out.ctypes.data, 4 * w, 0, None),
               "sr_accum_resolve")
+    return out
+
+
+def shutter_phases(ss: int, sub_frames: int):
+    """sr_shutter_phases: the default phase pairs of a shutter frame's
+    sub_frames sub-frames, uint8 [sub_frames, 2] {x, y}: sr_phase_order(ss, k
+    mod ss * ss)."""
+    import numpy as np
+
+    out = np.zeros((max(int(sub_frames), 0), 2), dtype=np.uint8)
+    check(load().sr_shutter_phases(int(ss), int(sub_frames), out.ctypes.data), "sr_shutter_phases")
+    return out
+
+
+def shutter_resolve(images, sub_frames: int):
+    """sr_shutter_resolve's host form: uint8 sub-frame images [M * sub_frames,
+    rows, W, 4] (host array) -> the M shutter frames [M, rows, W, 4], frame m
+    the rounded mean of images m * sub_frames .. (m + 1) * sub_frames - 1."""
+    import numpy as np
+
+    a = np.ascontiguousarray(images, dtype=np.uint8)
+    k = int(sub_frames)
+    if a.ndim != 4 or a.shape[-1] != 4 or k < 1 or a.shape[0] % k or a.shape[0] == 0:
+        raise ValueError(f"expected [M * {k}, rows, W, 4] images, got {a.shape}")
+    n, rows, w, _ = a.shape
+    out = np.empty((n // k, rows, w, 4), dtype=np.uint8)
+    if rows and w:
+        check(load().sr_shutter_resolve(a.ctypes.data, 4 * w, 4 * w * rows, k, n // k, w, rows, out.ctypes.data, 4 * w,
+                                        4 * w * rows, 0, None), "sr_shutter_resolve")
     return out
 
 

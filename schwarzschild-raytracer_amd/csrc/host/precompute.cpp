@@ -766,7 +766,9 @@ void derive_frame(const FrameInputs& in, const sr_dev_scene& sc, sr_dev_frame& f
     std::memset(&fr, 0, sizeof fr);
     for (int j = 0; j < SR_MAX_BUDGET; j++) fr.xlow_need[j] = INFINITY;  // low_energy_exclusions: the caller's
     for (int j = 0; j < SR_MAX_BUDGET; j++) fr.xperi_e[j] = -1.0f;
-    for (int f = 0; f < in.n_frames; f++) build_cam(in.phases ? in.cams[0] : in.cams[f], fr.cam[f]);
+    // a phase launch has one camera for every frame, unless its frames carry their own (FrameInputs::phase_cams)
+    const bool one_cam = in.phases && !in.phase_cams;
+    for (int f = 0; f < in.n_frames; f++) build_cam(one_cam ? in.cams[0] : in.cams[f], fr.cam[f]);
     fr.batch = in.n_frames;
     // frag:860 (launch invariant, same float ops)
     fr.max_angle = 2.0f * (float)p->max_revolutions * kPi;
@@ -833,7 +835,7 @@ void derive_frame(const FrameInputs& in, const sr_dev_scene& sc, sr_dev_frame& f
     fr.num_budget_cyl = __builtin_popcount((unsigned)sc.budget_cyl_mask);
     fr.tr_visible = sc.tr_visible ? 1 : 0;
     fr.projection = in.projection;
-    for (int f = 0; f < in.n_frames; f++) fr.cam_a[f] = sr::projection_half_angle((in.phases ? in.cams[0] : in.cams[f]).fov);
+    for (int f = 0; f < in.n_frames; f++) fr.cam_a[f] = sr::projection_half_angle((one_cam ? in.cams[0] : in.cams[f]).fov);
     // the black hole's u window (geodesic.hip SR_BH_WINDOW): chord origins within r = 100
     fr.win_ok = fr.uf_radius <= 100.0f;
     for (int f = 0; f < in.n_frames; f++) {

@@ -34,7 +34,7 @@ int check_frame_args(const sr_camera* cam, const sr_params* p, int width, int he
 
 // What a launch's frame struct takes from its arguments and the scene alone
 struct FrameInputs {
-    const sr_camera* cams;  // n_frames cameras, or one for every frame of a phase launch
+    const sr_camera* cams;  // n_frames cameras, or one for every frame of a phase launch (phase_cams unset)
     int n_frames;
     const sr_params* params;
     int width, height;
@@ -42,6 +42,8 @@ struct FrameInputs {
     const uint8_t* phases;  // n_frames byte pairs {x, y}, or null
     bool cull;
     int projection;
+    // a phase launch whose frame f has the camera cams[f] (sr.h "Shutter frames"), not cams[0]
+    bool phase_cams = false;
 };
 // Zeroes `fr` and sets the cameras, the schedule's constants and margins
 // (xplane_s, out_dip, max_dphi, bh_u2 / bh_u3, win_ok), the cull-off

@@ -71,6 +71,14 @@ void sr_accum_add_host(const uint8_t* images, size_t pitch, size_t image_stride,
 void sr_accum_resolve_host(const uint16_t* accum, size_t accum_pitch, int width, int rows, int n, uint8_t* out,
                            size_t pitch);
 
+// ---- shutter.hip
+// the group resolve of sr.h "Shutter frames": n_frames * sub_frames images to n_frames frames
+hipError_t sr_shutter_resolve_device(const uint8_t* images, size_t pitch, size_t image_stride, int sub_frames,
+                                     int n_frames, int width, int rows, const int* dev_blocks, int block_rows, int height,
+                                     uint8_t* out, size_t out_pitch, size_t out_frame_stride, hipStream_t stream);
+void sr_shutter_resolve_host(const uint8_t* images, size_t pitch, size_t image_stride, int sub_frames, int n_frames,
+                             int width, int rows, uint8_t* out, size_t out_pitch, size_t out_frame_stride);
+
 // ---- adaptive.hip
 hipError_t sr_edge_tiles_device(const uint8_t* img, size_t pitch, int width, int height, int threshold, int grow,
                                 uint8_t* dev_mask, hipStream_t stream);

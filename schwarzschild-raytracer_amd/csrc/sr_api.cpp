@@ -19,6 +19,7 @@
 #include "device_scene.h"
 #include "host/precompute.h"
 #include "kernels/launchers.h"
+#include "kernels/shutter_div.h"
 #include "sr/projection.hpp"
 #include "sr/sr.h"
 
@@ -503,6 +504,9 @@ struct Launch {
     // height and the rows are the output frame's
     int grid = 1;
     const uint8_t* phases = nullptr;
+    // the sub-frames of shutter frames (sr.h "Shutter frames"): a phase launch
+    // whose frame f has the camera cams[f], and under a sequence its scene
+    bool phase_cams = false;
     // a sequence launch (sr.h "Scene sequences"; -1: none): frame f renders
     // scene seq_first + f of the context's sequence, not its own scene
     int seq_first = -1;
@@ -568,7 +572,7 @@ int build_frame(sr_ctx* ctx, const Launch& r, sr_dev_frame& fr) {
     const int rc = check_frames(ctx, r.cams, r.n_frames, r.params, r.width, r.height, r.seq_first);
     if (rc != SR_OK) return rc;
     const bool seq = r.seq_first != -1;
-    if (seq && (r.phases || r.d_codes || r.d_wave_cost)) return SR_E_INVALID;
+    if (seq && (r.d_codes || r.d_wave_cost)) return SR_E_INVALID;
     if (r.phases) {
         if (r.grid < 1 || r.grid > SR_MAX_SUPERSAMPLE || r.width > INT32_MAX / (2 * r.grid) ||
             r.height > INT32_MAX / (2 * r.grid))
@@ -581,7 +585,8 @@ int build_frame(sr_ctx* ctx, const Launch& r, sr_dev_frame& fr) {
     if (r.out && r.pitch < (size_t)r.width * 4) return SR_E_INVALID;
     if (r.n_frames > 1 && (!r.out || r.frame_stride < r.pitch * (size_t)r.nrows || r.dbg_rgba || r.dbg_steps))
         return SR_E_INVALID;
-    sr_pre::derive_frame({r.cams, r.n_frames, r.params, r.width, r.height, r.grid, r.phases, ctx->cull, ctx->projection},
+    sr_pre::derive_frame({r.cams, r.n_frames, r.params, r.width, r.height, r.grid, r.phases, ctx->cull, ctx->projection,
+                          r.phase_cams},
                          seq ? ctx->h_seq[(size_t)r.seq_first] : ctx->h_scene, fr);
     if (seq) {
         // the slot counts pick the integrate kernel's capacity: the window's
@@ -1283,6 +1288,171 @@ int sr_phase_order(int ss, int k, int* phase_x, int* phase_y) {
     return SR_OK;
 }
 
+// ---- shutter frames (sr.h): the sub-frames are ONE phase launch whose frames
+// carry their own cameras and, under a sequence, their own scenes
+// (Launch::phase_cams) into the context's sample scratch; shutter.hip resolves
+// each group of sub_frames images to its output frame, or accum.hip adds them
+// to the caller's accumulator, on the same stream
+
+int sr_shutter_phases(int ss, int sub_frames, uint8_t* out_pairs) {
+    if (bad_grid(ss) || sub_frames < 1 || !out_pairs) return SR_E_INVALID;
+    for (int k = 0; k < sub_frames; k++) {
+        int x = 0, y = 0;
+        (void)sr_phase_order(ss, k % (ss * ss), &x, &y);
+        out_pairs[2 * k] = (uint8_t)x;
+        out_pairs[2 * k + 1] = (uint8_t)y;
+    }
+    return SR_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The sub-frame launch of the three shutter entry points: `groups` groups of
+// `sub` frames each (the accumulate form: one group), the caller's phases or
+// the default ones in `pairs`
+struct ShutterLaunch {
+    Launch r;
+    uint8_t pairs[2 * SR_MAX_BATCH];
+};
+
+// Every rejection of the sub-frames ahead of any allocation, and their launch
+// without its rows and output. (the status, then `out` on SR_OK)
+int shutter_frames(const sr_ctx* c, int first_scene, const sr_camera* cams, const uint8_t* phases, int sub, int groups,
+                   const sr_params* p, int width, int height, int ss, sr_stream stream, ShutterLaunch& out) {
+    if (!c || !cams || sub < 1 || groups < 1 || bad_grid(ss) || first_scene < SR_SHUTTER_OWN_SCENE) return SR_E_INVALID;
+    if ((long long)sub * groups > SR_MAX_BATCH) return SR_E_CAPACITY;
+    const int n = sub * groups;
+    if (phases) {
+        for (int f = 0; f < 2 * n; f++)
+            if (phases[f] >= ss) return SR_E_INVALID;
+        std::memcpy(out.pairs, phases, 2 * (size_t)n);
+    } else {
+        (void)sr_shutter_phases(ss, sub, out.pairs);
+        for (int g = 1; g < groups; g++) std::memcpy(out.pairs + 2 * (size_t)g * sub, out.pairs, 2 * (size_t)sub);
+    }
+    const bool own = first_scene == SR_SHUTTER_OWN_SCENE;
+    const int rc = check_frames(c, cams, n, p, width, height, own ? -1 : first_scene);
+    if (rc != SR_OK) return rc;
+    // build_frame's bounds of a phase launch
+    if (width > INT32_MAX / (4 * ss) || height > INT32_MAX / (2 * ss)) return SR_E_INVALID;
+    out.r = Launch(cams, n, p, width, height, stream);
+    out.r.grid = ss;
+    out.r.phases = out.pairs;
+    out.r.phase_cams = true;
+    if (!own) out.r.sequence(first_scene);
+    return SR_OK;
+}
+
+// The sub-frames into the sample scratch (rows and block list set in sl.r),
+// then their resolve to `groups` frames at `out`. No retained frame: the
+// sub-frames are not a caller's output.
+int launch_shutter(sr_ctx* c, ShutterLaunch& sl, int sub, int groups, uint8_t* out, size_t pitch, size_t frame_stride) {
+    Launch& r = sl.r;
+    c->kept.valid = false;
+    if (r.nrows == 0) return SR_OK;  // no rows: nothing is written
+    const hipStream_t s = reinterpret_cast<hipStream_t>(r.stream);
+    int rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    const size_t ipitch = (size_t)r.width * 4, istride = ipitch * (size_t)r.nrows;
+    rc = grow(c, c->d_ss, c->ss_bytes, istride * (size_t)r.n_frames, s);
+    if (rc != SR_OK) return rc;
+    rc = launch(c, r.into(c->d_ss, ipitch, istride));
+    c->kept.valid = false;
+    if (rc != SR_OK) return rc;
+    // again at the end of the whole: a launch on another stream waits for the resolve too
+    return finish(c, sr_shutter_resolve_device(c->d_ss, ipitch, istride, sub, groups, r.width, r.nrows, r.d_block_list,
+                                               r.block_rows, r.height, out, pitch, groups > 1 ? frame_stride : 0, s),
+                  s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sr_render_shutter(sr_ctx* c, int first_scene, const sr_camera* cams, const uint8_t* phases, int sub_frames,
+                      int n_frames, const sr_params* p, int width, int height, int row_begin, int row_end, int ss,
+                      uint8_t* out, size_t pitch, size_t frame_stride, sr_stream stream) {
+    if (!out || bad_rows(row_begin, row_end, height)) return SR_E_INVALID;
+    ShutterLaunch sl;
+    const int rc = shutter_frames(c, first_scene, cams, phases, sub_frames, n_frames, p, width, height, ss, stream, sl);
+    if (rc != SR_OK) return rc;
+    const int n = row_end - row_begin;
+    if (pitch < (size_t)width * 4 || n > (1 << 24) || (((uintptr_t)out | pitch) & 3) != 0) return SR_E_INVALID;
+    if (n_frames > 1 && (frame_stride < pitch * (size_t)n || (frame_stride & 3) != 0)) return SR_E_INVALID;
+    sl.r.band(row_begin, n);
+    return launch_shutter(c, sl, sub_frames, n_frames, out, pitch, frame_stride);
+}
+
+int sr_render_shutter_block_list(sr_ctx* c, int first_scene, const sr_camera* cams, const uint8_t* phases,
+                                 int sub_frames, int n_frames, const sr_params* p, int width, int height,
+                                 int block_rows, const int* blocks, int n_blocks, int ss, uint8_t* out, size_t pitch,
+                                 size_t frame_stride, sr_stream stream) {
+    int rc = check_block_list(c, out, blocks, n_blocks, block_rows, height, 1);
+    if (rc != SR_OK) return rc;
+    ShutterLaunch sl;
+    rc = shutter_frames(c, first_scene, cams, phases, sub_frames, n_frames, p, width, height, ss, stream, sl);
+    if (rc != SR_OK) return rc;
+    if (pitch < (size_t)width * 4 || (((uintptr_t)out | pitch) & 3) != 0) return SR_E_INVALID;
+    if (n_frames > 1 && (frame_stride < pitch * (size_t)(n_blocks * block_rows) || (frame_stride & 3) != 0))
+        return SR_E_INVALID;
+    const int* d = nullptr;
+    rc = ensure_block_list(c, blocks, n_blocks, stream, &d);
+    if (rc != SR_OK) return rc;
+    sl.r.block_list(d, n_blocks, block_rows);
+    return launch_shutter(c, sl, sub_frames, n_frames, out, pitch, frame_stride);
+}
+
+int sr_render_accumulate_shutter(sr_ctx* c, int first_scene, const sr_camera* cams, const uint8_t* phases, int n_sub,
+                                 const sr_params* p, int width, int height, int row_begin, int row_end, int ss, int reset,
+                                 uint16_t* accum, size_t accum_pitch, sr_stream stream) {
+    if (!accum || bad_rows(row_begin, row_end, height)) return SR_E_INVALID;
+    ShutterLaunch sl;
+    int rc = shutter_frames(c, first_scene, cams, phases, n_sub, 1, p, width, height, ss, stream, sl);
+    if (rc != SR_OK) return rc;
+    if (width > INT32_MAX / 8 || accum_pitch < (size_t)width * 8 || (((uintptr_t)accum | accum_pitch) & 7) != 0)
+        return SR_E_INVALID;
+    const int n = row_end - row_begin;
+    if (n > (1 << 24)) return SR_E_INVALID;
+    c->kept.valid = false;  // the sub-frames are not a caller's output: nothing is retained
+    if (n == 0) return SR_OK;  // no rows: nothing is written
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    const size_t ipitch = (size_t)width * 4, istride = ipitch * (size_t)n;
+    rc = grow(c, c->d_ss, c->ss_bytes, istride * (size_t)n_sub, s);
+    if (rc != SR_OK) return rc;
+    rc = launch(c, sl.r.band(row_begin, n).into(c->d_ss, ipitch, istride));
+    c->kept.valid = false;
+    if (rc != SR_OK) return rc;
+    // again at the end of the whole: a launch on another stream waits for the add too
+    return finish(c, sr_accum_add_device(c->d_ss, ipitch, istride, n_sub, width, n, reset ? 1 : 0, accum, accum_pitch, s), s);
+}
+
+int sr_shutter_resolve(const uint8_t* images, size_t pitch, size_t image_stride, int sub_frames, int n_frames, int width,
+                       int rows, uint8_t* out, size_t out_pitch, size_t out_frame_stride, int on_device,
+                       sr_stream stream) {
+    if (!images || !out || width <= 0 || rows < 0 || sub_frames < 1 || sub_frames > SR_MAX_ACCUM_PASSES || n_frames < 1 ||
+        n_frames > 65535)
+        return SR_E_INVALID;
+    if (width > INT32_MAX / 4 || rows > (1 << 24) || pitch < (size_t)width * 4 || out_pitch < (size_t)width * 4)
+        return SR_E_INVALID;
+    const bool many = sub_frames > 1 || n_frames > 1;
+    if (many && image_stride < pitch * (size_t)rows) return SR_E_INVALID;
+    if (n_frames > 1 && out_frame_stride < out_pitch * (size_t)rows) return SR_E_INVALID;
+    if ((((uintptr_t)images | pitch | (many ? image_stride : 0)) & 3) != 0) return SR_E_INVALID;
+    if ((((uintptr_t)out | out_pitch | (n_frames > 1 ? out_frame_stride : 0)) & 3) != 0) return SR_E_INVALID;
+    if (!on_device)
+        return sr_shutter_resolve_host(images, pitch, image_stride, sub_frames, n_frames, width, rows, out, out_pitch,
+                                       out_frame_stride),
+               SR_OK;
+    // a stride nothing is read at does not pick the path
+    return status(sr_shutter_resolve_device(images, pitch, many ? image_stride : 0, sub_frames, n_frames, width, rows,
+                                            nullptr, 0, rows, out, out_pitch, n_frames > 1 ? out_frame_stride : 0,
+                                            reinterpret_cast<hipStream_t>(stream)));
+}
+
 // ---- adaptive supersampling: the plain frame P into the caller's buffer,
 // the selection of its edge tiles (adaptive.hip), a sparse launch of the
 // sample frame for the flagged tiles only, and their masked resolve over P,
@@ -1701,6 +1871,13 @@ int sr_debug_frame(const sr_scene* s, const sr_test_ray* t, const sr_camera* cam
                      fr);
     if (rc == SR_OK) std::memcpy(frame_out, &fr, sizeof fr);
     return rc;
+}
+
+// The shutter resolve's division as the kernel computes it (kernels/shutter_div.h):
+// n div k for n < 2^16, k in 1 .. 256; -1 outside
+int sr_debug_shutter_div(int n, int k) {
+    if (n < 0 || n > 0xffff || k < 1 || k > 256) return -1;
+    return (int)sr_shutter_div((uint32_t)n, sr_shutter_magic((uint32_t)k));
 }
 
 // The step table of a schedule: 4 * (max_steps + 4) floats

@@ -459,6 +459,105 @@ class Renderer:
         )
         return f, b, s
 
+    # ---- shutter frames (sr.h): motion blur and anti-aliasing from one batched launch ----
+    def _shutter_args(self, cams, sub_frames: int, phases):
+        """(camera array, phase bytes or None, M) of M * sub_frames sub-frames."""
+        n, k = len(cams), int(sub_frames)
+        if k < 1 or n < 1 or n % k:
+            raise ValueError(f"expected M * {k} cameras, got {n}")
+        arr = (abi.Camera * n)(*cams)
+        ph = None
+        if phases is not None:
+            flat = [int(v) for pair in phases for v in pair]
+            if len(flat) != 2 * n:
+                raise ValueError(f"expected {n} phase pairs, got {len(flat) // 2}")
+            ph = (C.c_uint8 * len(flat))(*flat)
+        return arr, ph, n // k
+
+    def render_shutter(self, first_scene: int, cams, sub_frames: int, params: abi.Params, width: int, height: int,
+                       ss: int = 1, phases=None, row_begin: int = 0, row_end: int | None = None, out=None, stream=None):
+        """sr_render_shutter: rows [row_begin, row_end) of M = len(cams) //
+        sub_frames shutter frames in one launch; frame m is the rounded mean of
+        its sub_frames sub-frames, sub-frame j of scene first_scene + j of the
+        sequence (abi.SHUTTER_OWN_SCENE: the context's own scene) with cams[j]
+        and phase phases[j] of the ss x ss grid (None: the progressive order)
+        -> [M, rows, W, 4]. Asynchronous."""
+        row_end = height if row_end is None else row_end
+        rows = max(row_end - row_begin, 0)
+        arr, ph, M = self._shutter_args(cams, sub_frames, phases)
+        if out is None:
+            out = self.torch.empty((M, rows, width, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and tuple(out.shape[:1]) == (M,)
+        assert out[0].numel() >= rows * width * 4
+        abi.check(
+            self.lib.sr_render_shutter(self.ctx, int(first_scene), arr, ph, int(sub_frames), M, C.byref(params), width,
+                                       height, row_begin, row_end, int(ss), C.c_void_p(out.data_ptr()), width * 4,
+                                       out[0].numel(), self._stream(stream)),
+            "sr_render_shutter",
+        )
+        return out
+
+    def render_shutter_block_list(self, first_scene: int, cams, sub_frames: int, params: abi.Params, width: int,
+                                  height: int, block_rows: int, blocks, ss: int = 1, phases=None, out=None,
+                                  stream=None):
+        """render_shutter for the rows of an explicit block list (-1 = padding)
+        -> [M, len(blocks) * block_rows, W, 4]."""
+        blocks = [int(b) for b in blocks]
+        arr, ph, M = self._shutter_args(cams, sub_frames, phases)
+        lst = (C.c_int * len(blocks))(*blocks)
+        rows = len(blocks) * block_rows
+        if out is None:
+            out = self.torch.empty((M, rows, width, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and tuple(out.shape[:1]) == (M,)
+        assert out[0].numel() >= rows * width * 4
+        abi.check(
+            self.lib.sr_render_shutter_block_list(self.ctx, int(first_scene), arr, ph, int(sub_frames), M,
+                                                  C.byref(params), width, height, block_rows, lst, len(blocks), int(ss),
+                                                  C.c_void_p(out.data_ptr()), width * 4, out[0].numel(),
+                                                  self._stream(stream)),
+            "sr_render_shutter_block_list",
+        )
+        return out
+
+    def accumulate_shutter(self, first_scene: int, cams, params: abi.Params, width: int, height: int, ss: int = 1,
+                           phases=None, accum=None, reset: bool = False, row_begin: int = 0,
+                           row_end: int | None = None, stream=None):
+        """sr_render_accumulate_shutter: the len(cams) (at most abi.MAX_BATCH)
+        sub-frames of one group in one launch, added to `accum` (new_accum; a
+        new one when None), or stored over it when reset -> accum. Resolve
+        with accum_resolve and the number of sub-frames added."""
+        row_end = height if row_end is None else row_end
+        rows = row_end - row_begin
+        if accum is None:
+            accum, reset = self.new_accum(width, max(rows, 0)), True
+        assert self._check_accum(accum) == (max(rows, 0), width)
+        arr, ph, _ = self._shutter_args(cams, len(cams), phases)
+        abi.check(
+            self.lib.sr_render_accumulate_shutter(self.ctx, int(first_scene), arr, ph, len(cams), C.byref(params), width,
+                                                  height, row_begin, row_end, int(ss), 1 if reset else 0,
+                                                  C.c_void_p(accum.data_ptr()), width * 8, self._stream(stream)),
+            "sr_render_accumulate_shutter",
+        )
+        return accum
+
+    def shutter_resolve(self, images, sub_frames: int, out=None, stream=None):
+        """sr_shutter_resolve on the device: uint8 images [M * sub_frames, rows,
+        W, 4] on this device -> the M frames [M, rows, W, 4]. Asynchronous."""
+        assert images.dtype == self.torch.uint8 and images.dim() == 4 and images.shape[3] == 4 and images.is_contiguous()
+        n, rows, w = (int(v) for v in images.shape[:3])
+        k = int(sub_frames)
+        if k < 1 or n < 1 or n % k:
+            raise ValueError(f"expected M * {k} images, got {n}")
+        if out is None:
+            out = self.torch.empty((n // k, rows, w, 4), dtype=self.torch.uint8, device=self.tdev)
+        assert out.is_contiguous() and out.dtype == self.torch.uint8 and out.numel() >= (n // k) * rows * w * 4
+        abi.check(
+            self.lib.sr_shutter_resolve(C.c_void_p(images.data_ptr()), 4 * w, 4 * w * rows, k, n // k, w, rows,
+                                        C.c_void_p(out.data_ptr()), 4 * w, 4 * w * rows, 1, self._stream(stream)),
+            "sr_shutter_resolve",
+        )
+        return out
+
     # ---- retained frames (sr.h): relight and pick from the last launch's rays ----
     def can_reshade(self) -> bool:
         """sr_can_reshade: the context holds a retained frame reshade() would accept."""

@@ -20,6 +20,11 @@ hyperbolic trajectory (src/main.cpp:404-410) in batched launches.
   python tools/render.py --orbit-frames 48 --out orbit_%02d.png
                                   (the default scene's sphere on a circular orbit: the scenes as one
                                    sequence, sr_set_scene_sequence, rendered 32 frames per launch)
+  python tools/render.py --orbit-frames 24 --shutter 4 --ssaa 2 --out blur_%02d.png
+  python tools/render.py --flyby 8 --shutter 16 --ssaa 4 --shutter-angle 180 --out flyby_blur_%02d.png
+                                  (shutter frames, sr_render_shutter: every frame the mean of K sub-frames at
+                                   times spread over the shutter's open part of the frame interval, each with
+                                   its own scene or camera and its own sub-pixel phase of the --ssaa grid)
 """
 import argparse
 import math
@@ -105,7 +110,21 @@ def main():
     ap.add_argument("--focus", type=float, default=10.0, metavar="D",
                     help="--aperture: the distance along each pixel's pinhole ray that stays sharp")
     ap.add_argument("--lens-samples", type=int, default=16, metavar="K", help="--aperture: lens samples per pixel")
+    ap.add_argument("--shutter", type=int, default=0, metavar="K",
+                    help="with --orbit-frames or --flyby: motion blur, every frame the mean of K (1 .. 32) sub-frames "
+                         "(sr_render_shutter); sub-frame k of frame m of N is at time (m + (k + 1/2) / K * DEG / 360) / N "
+                         "and takes phase k of the --ssaa grid in sr_phase_order")
+    ap.add_argument("--shutter-angle", type=float, default=360.0, metavar="DEG",
+                    help="--shutter: the part of the frame interval the shutter is open, in degrees of 360")
     args = ap.parse_args()
+    if args.shutter:
+        if not 1 <= args.shutter <= 32 or not 0.0 <= args.shutter_angle <= 360.0:
+            ap.error("--shutter takes 1 .. 32 sub-frames (SR_MAX_BATCH) and --shutter-angle 0 .. 360 degrees")
+        if bool(args.orbit_frames) == (args.flyby > 0) or args.adaptive is not None or args.progressive is not None \
+                or args.aperture is not None:
+            ap.error("--shutter blurs the frames of --orbit-frames or of --flyby")
+        if args.orbit_frames * args.shutter > 256:
+            ap.error("--orbit-frames x --shutter scenes must fit a sequence (SR_MAX_SEQUENCE = 256)")
     if args.aperture is not None:
         if (args.flyby > 0 or args.adaptive is not None or args.progressive is not None or args.orbit_frames or
                 args.ssaa != 1 or args.projection != "rectilinear" or args.crosshair or args.percent_black >= 0.0 or
@@ -149,7 +168,38 @@ def main():
             cam.fov = args.fov
         return cam
 
-    if args.aperture is not None:
+    def write_frames(out, first):
+        torch.cuda.synchronize()
+        for k, fr in enumerate(out.cpu().numpy()):
+            path = args.out % (first + k) if "%" in args.out else f"{Path(args.out).stem}_{first + k:03d}.png"
+            abi.write_png(path, fr)
+            print(f"wrote {path}")
+
+    def orbit_scene(t):
+        """The default scene with its sphere at turn t of a circle about the hole, in the plane and at the distance it starts at"""
+        s = sc.scene_default(textured=True)
+        pos = s.spheres[0].transform.pos
+        radius, phase = math.hypot(pos[0], pos[2]), math.atan2(pos[2], pos[0])
+        pos[0] = radius * math.cos(phase + 2.0 * math.pi * t)
+        pos[2] = radius * math.sin(phase + 2.0 * math.pi * t)
+        return s
+
+    if args.shutter:
+        K = args.shutter
+        n = args.orbit_frames or args.flyby
+        times = [(j // K + ((j % K) + 0.5) / K * args.shutter_angle / 360.0) / n for j in range(n * K)]
+        if args.orbit_frames:  # a scene per sub-frame, one camera
+            r.set_scene_sequence([orbit_scene(t) for t in times])
+            cams = [camera()] * (n * K)
+        else:  # the context's own scene, the flyby camera at the sub-frames' times
+            cams = [abi.camera_flyby(t, 30.0, 10.0, cam=camera()) for t in times]
+        per = max(1, 32 // K)  # frames per launch: 32 sub-frames
+        for first in range(0, n, per):
+            m = min(per, n - first)
+            out = r.render_shutter(first * K if args.orbit_frames else abi.SHUTTER_OWN_SCENE,
+                                   cams[first * K:(first + m) * K], K, params, W, H, args.ssaa)
+            write_frames(out, first)
+    elif args.aperture is not None:
         frame = thin_lens_frame(pkg, r, camera(), params, W, H, args.aperture, args.focus, args.lens_samples)
         torch.cuda.synchronize()
         abi.write_png(args.out, frame.cpu().numpy())
