@@ -666,6 +666,80 @@ int sr_reshade_debug(sr_ctx* ctx, float* dev_rgba32, uint8_t* dev_rgba8, int32_t
 #define SR_PICK_NONE            (-5)  /* no ray: a pixel the noise mask blacked out */
 int sr_pick_map(sr_ctx* ctx, int32_t* dev_ids, size_t pitch_bytes, size_t frame_stride_bytes, sr_stream stream);
 
+/* ---- Ray maps (not in the reference, whose only output is the colour). What
+ * the retained rays know besides a colour and an object code: where on the sky
+ * each pixel's bent ray ends (the lens map) and the G-buffer of its first
+ * surface, in one cheap pass over the record, without walking a geodesic that
+ * already ended.
+ *
+ * Definition. The maps describe the pixels of the retained launch in the
+ * shader's own walk (frag:930-932). "First surface" is exactly sr_pick_map's:
+ * a single-sided surface seen from behind is not one.
+ *  - id equals sr_pick_map everywhere.
+ *  - end is SR_RAY_END_SKY where the pixel's colour ends with a get_bg(dir)
+ *    term: rays seen through translucent surfaces, flat rays whose intersect
+ *    returned alpha != 1, rays that left the loop by u < 0 or ran out of steps
+ *    (frag:935) included; SR_RAY_END_OPAQUE where it ended at a surface whose
+ *    shaded alpha is exactly 1 (an object, the hole, a test ray);
+ *    SR_RAY_END_NONE where the pixel has no ray (sr_pick_map's SR_PICK_NONE).
+ *  - sky_dir and sky_uv are valid where end == SR_RAY_END_SKY: the argument of
+ *    that get_bg call and its (u, v) by sr_sky_uv's expressions. Elsewhere they
+ *    hold the quiet NaN 0x7fc00000.
+ *  - the hit_* maps are valid where id >= 0 and describe that surface; elsewhere
+ *    the float maps hold the quiet NaN 0x7fc00000 and hit_step holds -1.
+ *    Validity is read from id, never from a NaN: a real value may be NaN under
+ *    a non-finite camera.
+ *  - hit_step is the value sr_render_debug's step count would have if the ray
+ *    ended at that surface: it equals the pixel's step count when hit_base's
+ *    alpha is 1, and is 0 in flat mode.
+ *  - Deferred shading: where id >= 0, hit_base's alpha is 1 and the crosshair
+ *    is off, the pixel's float FragColor rgb is calculate_lighting (frag:406-437)
+ *    evaluated on hit_point, hit_normal, hit_view and hit_base with the
+ *    object's material terms and the scene's lights, in binary32, in the
+ *    shader's order; FragColor.a is 1.
+ *  - hit_base, hit_normal and sky_uv follow the context's current scene,
+ *    texture array and filter mode, as a reshade does; the rest depends on the
+ *    retained rays only.
+ * Layout: rows, batch, block list, the -1 padding and the rows past the
+ * frame's end left unwritten are the retained launch's, as for sr_pick_map.
+ * Element (pixel x, output row k, frame f, component c) of a map with n
+ * components is at map[(f * frame_stride_pixels + k * pitch_pixels + x) * n +
+ * c]; one pitch, in pixels, serves all maps. Only the maps whose pointer is
+ * not NULL are written.
+ *
+ * The retained frame stays valid, no launch order is learned or touched and
+ * sr_diag_counters keeps its meaning. Asynchronous on `stream`, no host wait,
+ * ordered like every launch of the context. A pixel whose hit log filled with
+ * translucent hits is walked on from its stored state, which is read and not
+ * written: a later sr_reshade sees the same record.
+ *
+ * Nothing is launched or written on a rejection. SR_E_INVALID: a null context
+ * or struct, all pointers null, a pointer not 4-byte aligned, pitch_pixels <
+ * width or, for a batch, frame_stride_pixels < pitch_pixels * rows.
+ * SR_E_NOT_READY: no retained frame, or a retained supersampled launch, as
+ * sr_pick_map. */
+#define SR_RAY_END_NONE   0  /* no ray: the noise mask, a fisheye pixel beyond PI */
+#define SR_RAY_END_SKY    1  /* the pixel's colour ends with a get_bg(dir) term */
+#define SR_RAY_END_OPAQUE 2  /* it ended at a surface of alpha exactly 1 (object, hole, test ray) */
+typedef struct {
+    int32_t* end;        /* 1 per pixel: SR_RAY_END_*                                  */
+    int32_t* id;         /* 1: sr_pick_map's code of the first surface                  */
+    float*   sky_dir;    /* 3: the argument of the pixel's get_bg call (frag:876/897/905/935) */
+    float*   sky_uv;     /* 2: get_bg's (u, v), frag:830-834, under the arithmetic contract  */
+    float*   hit_point;  /* 3: hit_info.intersection_point of the first surface         */
+    float*   hit_normal; /* 3: `normal` of frag:408-413 (after flip_normals and the normal map) */
+    float*   hit_view;   /* 3: view_dir, = -dir of the chord or flat ray that hit       */
+    float*   hit_base;   /* 4: base_color of frag:382-405 (rgb albedo, a = the hit's alpha) */
+    int32_t* hit_step;   /* 1: geodesic steps the pixel had executed when this surface was found */
+} sr_ray_map_ptrs;       /* device pointers, any of them NULL but not all */
+int sr_ray_maps(sr_ctx* ctx, const sr_ray_map_ptrs* maps, size_t pitch_pixels,
+                size_t frame_stride_pixels, sr_stream stream);
+/* Host only, no context: get_bg's (u, v) of a direction, the code the kernel
+ * runs (include/sr/sky.hpp): atan2 and asin are the binary64 function rounded
+ * to binary32; u = atan2(z, x) / PI, + 2 when negative, * 0.5; v = asin(y) /
+ * PI + 0.5. The direction is not normalised. SR_E_INVALID on null arguments. */
+int sr_sky_uv(const float dir[3], float out_uv[2]);
+
 /* Split tiles (not in the reference; a latency knob, the pixels are unchanged):
  * the next frames run the max_tiles costliest 16x16 workgroup tiles of the
  * previous frame on this context whose longest ray took at least min_steps

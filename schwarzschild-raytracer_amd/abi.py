@@ -166,6 +166,17 @@ class TestRay(C.Structure):
     ]
 
 
+# sr_ray_map_ptrs (sr.h "Ray maps"): device pointers, any of them null; the
+# components per pixel and the element type of each map
+RAY_MAPS = {"end": (1, "int32"), "id": (1, "int32"), "sky_dir": (3, "float32"), "sky_uv": (2, "float32"),
+            "hit_point": (3, "float32"), "hit_normal": (3, "float32"), "hit_view": (3, "float32"),
+            "hit_base": (4, "float32"), "hit_step": (1, "int32")}
+
+
+class RayMapPtrs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in RAY_MAPS]
+
+
 # Functions declared in include/sr/sr.h: name -> (restype, argtypes)
 _p = C.c_void_p
 _i = C.c_int
@@ -240,6 +251,8 @@ SIGNATURES = {
                                           _p, C.c_size_t, _p]),
     "sr_shutter_resolve": (_i, [_p, C.c_size_t, C.c_size_t, _i, _i, _i, _i, _p, C.c_size_t, C.c_size_t, _i, _p]),
     "sr_shutter_phases": (_i, [_i, _i, _p]),
+    "sr_ray_maps": (_i, [_p, C.POINTER(RayMapPtrs), C.c_size_t, C.c_size_t, _p]),
+    "sr_sky_uv": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 # sr_set_projection's values (sr.h "Projections")
 PROJECTION_RECTILINEAR, PROJECTION_EQUIRECT, PROJECTION_FISHEYE = 0, 1, 2
@@ -252,7 +265,10 @@ SINCE_SEQUENCES = ("sr_set_scene_sequence", "sr_scene_sequence_length", "sr_rend
 SINCE_TRACE = ("sr_trace_rays", "sr_camera_rays")
 SINCE_SHUTTER = ("sr_render_shutter", "sr_render_shutter_block_list", "sr_render_accumulate_shutter",
                  "sr_shutter_resolve", "sr_shutter_phases")
-SHUTTER_OWN_SCENE = -1  # sr_render_shutter's first_scene for the context's own scene (sr.h "Shutter frames")
+SINCE_RAY_MAPS = ("sr_ray_maps", "sr_sky_uv")
+# sr_ray_maps' `end` codes (sr.h "Ray maps")
+RAY_END_NONE, RAY_END_SKY, RAY_END_OPAQUE = 0, 1, 2
+SHUTTER_OWN_SCENE = -1 # sr_render_shutter's first_scene for the context's own scene (sr.h "Shutter frames")
 TRACE_MAX_RAYS = 1 << 28  # rays of one trace launch (sr.h "Ray queries")
 MAX_SEQUENCE = 256  # scenes of a sequence (sr.h "Scene sequences")
 # sr_pick_map's codes below the indices into scene.objects[]
@@ -302,7 +318,7 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
     lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **EXTRA_SIGNATURES}.items():
         if (name in EXTRA_SIGNATURES or name in SINCE_PROJECTIONS or name in SINCE_SEQUENCES or
-                name in SINCE_TRACE or name in SINCE_SHUTTER) and not hasattr(lib, name):
+                name in SINCE_TRACE or name in SINCE_SHUTTER or name in SINCE_RAY_MAPS) and not hasattr(lib, name):
             continue  # debug tooling and newer calls an older library (a bisection build) may lack
         fn = getattr(lib, name)
         fn.restype = res
@@ -336,6 +352,18 @@ def projection_dir(projection: int, fov: float, uv_width: int, uv_height: int, p
     if rc < 0:
         raise SRError(rc, "sr_projection_dir")
     return out if rc == 1 else None
+
+
+def sky_uv(direction):
+    """sr_sky_uv: get_bg's (u, v) (float32 [2]) of a direction (3 floats, taken
+    as it is, not normalised), the code the ray-map kernels run. Host only."""
+    import numpy as np
+
+    d = np.ascontiguousarray(direction, dtype=np.float32).reshape(3)
+    out = np.zeros(2, dtype=np.float32)
+    check(load().sr_sky_uv(d.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float))),
+          "sr_sky_uv")
+    return out
 
 
 def camera_rays(cam: Camera, projection, width: int, height: int, row_begin: int = 0, row_end: int | None = None):

@@ -28,6 +28,7 @@ __device__ __forceinline__ float4 ldc(const sr_cfloat4* p) {
 #include "dispatch.h"
 #include "launchers.h"
 #include "sr/projection.hpp"
+#include "sr/sky.hpp"
 
 namespace {
 
@@ -75,6 +76,13 @@ __device__ __attribute__((noinline)) float t_pow(float x, float y) { return (flo
 // registers are the callee's, not the projected integrate instantiations'
 __device__ __attribute__((noinline)) float t_sin_ol(float x) { return t_sin(x); }
 __device__ __attribute__((noinline)) float t_cos_ol(float x) { return t_cos(x); }
+// sr/sky.hpp's atan2 and asin (get_bg's (u, v))
+struct SkyAtan2 {
+    __device__ float operator()(float y, float x) const { return t_atan2(y, x); }
+};
+struct SkyAsin {
+    __device__ float operator()(float x) const { return t_asin(x); }
+};
 struct ProjSin {
     __device__ __forceinline__ float operator()(float x) const { return t_sin_ol(x); }
 };
@@ -1917,12 +1925,10 @@ __device__ f4 bilinear(const uint32_t* base, int w, int h, float u, float v, int
 }
 // get_bg, frag:829-837
 __device__ __forceinline__ f4 get_bg(const sr_dev_frame& fr, const Tex& tx, f3 dir) {
-    float u = t_atan2(dir.z, dir.x) / SR_PI;
-    if (u < 0.0f) u += 2.0f;
-    u *= 0.5f;
-    float v = t_asin(dir.y) / SR_PI + 0.5f;
+    float uv[2];  // the one statement of (u, v): sr/sky.hpp, also sr_sky_uv's and the ray maps'
+    sr::sky_uv(dir.x, dir.y, dir.z, SkyAtan2(), SkyAsin(), uv);
     if (!tx.bg || fr.bg_w <= 0 || fr.bg_h <= 0) return F4(0.0f, 0.0f, 0.0f, 1.0f);
-    return bilinear(tx.bg, fr.bg_w, fr.bg_h, u, v, fr.filter_mode);
+    return bilinear(tx.bg, fr.bg_w, fr.bg_h, uv[0], uv[1], fr.filter_mode);
 }
 __device__ f4 tex_array(const sr_dev_frame& fr, const Tex& tx, f2 uv, int layer) {
     if (!tx.arr || fr.arr_w <= 0 || fr.arr_h <= 0 || fr.arr_layers <= 0) return F4(0.0f, 0.0f, 0.0f, 1.0f);
@@ -2155,6 +2161,71 @@ __device__ __forceinline__ f4 shade_hit(const sr_dev_scene* __restrict__ sc, con
         col = col + ((diffuse + specular) * att) * L.intensity;
     }
     return F4(col.x, col.y, col.z, base.w);
+}
+
+// The material half of shade_hit for an object's hit (h.slot >= 0), statement
+// for statement: base_color (frag:382-405) and `normal` (frag:408-413), for the
+// ray maps (sr.h "Ray maps"). `back`: a single-sided surface seen from behind
+// (shade_hit's vec4(0)); base and normal are then unset. The object record is
+// loaded per lane: nothing here asserts wave-uniformity, the callers' lanes are
+// unrelated pixels outside any waterfall. want_normal false skips the normal
+// map (a caller that reads the alpha alone).
+struct SurfaceMaterial {
+    f4 base;
+    f3 normal;
+    bool back;
+};
+__device__ SurfaceMaterial surface_material(const sr_dev_scene* __restrict__ sc, const sr_dev_frame& fr, const Tex& tx,
+                                            const Hit& h, f3 view_dir, bool want_normal) {
+    SurfaceMaterial g;
+    g.base = F4(0.0f, 0.0f, 0.0f, 0.0f);
+    g.normal = F3(0.0f, 0.0f, 0.0f);
+    g.back = false;
+    const sr_dev_obj& ob = sc->objs[h.slot];
+    int mi = ob.material_index;
+    if (mi < 0 || mi >= SR_MAX_MATERIALS) mi = 0;
+    const sr_material& m = sc->materials[mi];
+    Surface s = surface_of(ob, h);
+    if (m.flip_normals) s.n = s.n * -1.0f;
+    if (!m.double_sided_normals && dot(s.n, view_dir) < 0.0f) {
+        g.back = true;
+        return g;
+    }
+    f2 uv = s.uv;
+    const bool is_plane = ob.type == SR_OBJECT_PLANE;
+    int pi = ob.index;
+    if (pi < 0 || pi >= SR_MAX_PLANES) pi = 0;
+    const sr_plane& pl = sc->planes[pi];
+    if (m.swap_uvs) uv = F2(uv.y, uv.x);
+    if (m.invert_uv_x) uv.x = (is_plane ? pl.texture_size[0] : 1.0f) - uv.x;
+    if (m.invert_uv_y) uv.y = (is_plane ? pl.texture_size[1] : 1.0f) - uv.y;
+
+    f4 base = F4(m.color[0], m.color[1], m.color[2], m.color[3]);
+    if (m.texture_index >= 0) {
+        int ti = m.texture_index < SR_MAX_TEXTURES ? m.texture_index : 0;
+        f2 r = F2((uv.x * sc->texture_sizes[ti][0]) / sc->max_texture_size[0],
+                  (uv.y * sc->texture_sizes[ti][1]) / sc->max_texture_size[1]);
+        bool render = true;
+        if (is_plane) {
+            r = F2(r.x - pl.texture_offset[0], r.y - pl.texture_offset[1]);
+            f2 puv = F2(r.x / pl.texture_size[0], r.y / pl.texture_size[1]);
+            r.x = r.x - pl.texture_size[0] * floorf(r.x / pl.texture_size[0]);
+            r.y = r.y - pl.texture_size[1] * floorf(r.y / pl.texture_size[1]);
+            r = F2(r.x / pl.texture_size[0], r.y / pl.texture_size[1]);
+            render = pl.repeat_texture || ((puv.x >= 0.0f && puv.x <= 1.0f) && (puv.y >= 0.0f && puv.y <= 1.0f));
+        }
+        if (render) base = tex_array(fr, tx, r, m.texture_index);
+    }
+    g.base = base;
+    g.normal = s.n;
+    if (want_normal && m.normal_map_index >= 0) {
+        int ni = m.normal_map_index < SR_MAX_TEXTURES ? m.normal_map_index : 0;
+        f2 r = F2((uv.x * sc->texture_sizes[ni][0]) / sc->max_texture_size[0],
+                  (uv.y * sc->texture_sizes[ni][1]) / sc->max_texture_size[1]);
+        f4 nm = tex_array(fr, tx, r, m.normal_map_index);
+        g.normal = nrm(mv(surface_frame(ob, h, s, s.n), F3(nm.x, nm.y, nm.z)));
+    }
+    return g;
 }
 
 // calculate_lighting for the active lanes' hits: a waterfall over the distinct
@@ -4026,5 +4097,290 @@ extern "C" hipError_t sr_launch_trace(const sr_dev_scene* sc, const float4* tbl,
     hipLaunchKernelGGL(kernel, dim3(groups < SR_TRACE_GROUPS ? groups : SR_TRACE_GROUPS), dim3(SR_WG), 0, stream, sc, tbl,
                        segs, bg, arr, *fr, origins, dirs, n_rays, out_rgba, reinterpret_cast<uint32_t*>(out_rgba8), out_steps,
                        out_ids);
+    return hipGetLastError();
+}
+
+// ---- ray maps (sr.h "Ray maps"): the lens map and the first surface's
+// G-buffer from the pixel state a launch left. Emitted where
+// sr_launch_ray_maps instantiates them: after every other kernel, whose code
+// and addresses in the code object stay the parent's.
+
+namespace {
+
+#define RAY_END_NONE 0
+#define RAY_END_SKY 1
+#define RAY_END_OPAQUE 2
+
+// The alpha shade() gives a hit (shade_hit's .w): the hole 1, a test ray its
+// colour's, an object its base colour's, 0 for a single-sided surface seen
+// from behind. A ray ends where it is exactly 1 (frag:932).
+__device__ __forceinline__ float hit_alpha(const sr_dev_scene* __restrict__ sc, const sr_dev_frame& fr, const Tex& tx,
+                                           const Hit& h, f3 view_dir) {
+    if (h.slot == SLOT_BH) return 1.0f;
+    if (h.slot == SLOT_TR_CURVED) return sc->tr_curved_color[3];
+    if (h.slot == SLOT_TR_FLAT) return sc->tr_flat_color[3];
+    if (h.slot < 0 || h.slot >= SR_MAX_OBJECTS) return 0.0f;  // no such slot is logged (memory safety)
+    const SurfaceMaterial g = surface_material(sc, fr, tx, h, view_dir, false);
+    return g.back ? 0.0f : g.base.w;
+}
+
+// the maps' element of pixel (q.px, q.k) of frame f: pitch and stride in pixels
+__device__ __forceinline__ size_t ray_map_elem(const Pix& q, int f, size_t pitch, size_t frame_stride) {
+    return (size_t)f * frame_stride + (size_t)q.k * pitch + (size_t)q.px;
+}
+// end, sky_dir and sky_uv of one pixel (NaN-filled unless the ray ends in the sky), 4-byte stores
+__device__ __forceinline__ void put_ray_end(const sr_ray_map_ptrs& m, size_t e, int end, f3 dir) {
+    const float qn = __int_as_float(0x7fc00000);
+    const bool sky = end == RAY_END_SKY;
+    if (m.end) m.end[e] = end;
+    if (m.sky_dir) {
+        m.sky_dir[3 * e + 0] = sky ? dir.x : qn;
+        m.sky_dir[3 * e + 1] = sky ? dir.y : qn;
+        m.sky_dir[3 * e + 2] = sky ? dir.z : qn;
+    }
+    if (m.sky_uv) {
+        float uv[2] = {qn, qn};
+        if (sky) sr::sky_uv(dir.x, dir.y, dir.z, SkyAtan2(), SkyAsin(), uv);
+        m.sky_uv[2 * e + 0] = uv[0];
+        m.sky_uv[2 * e + 1] = uv[1];
+    }
+}
+
+}  // namespace
+
+// One lane per pixel id on sr_pick_kernel's grid. The walk of sr_shade_kernel
+// over the record without the lighting: the logged hits in order, each with
+// shade()'s alpha, then the ray's end (the hole, the flat intersect, the sky).
+// The first surface is sr_pick_kernel's: hit 0, or the flat intersect's
+// winner unless it is seen from behind. A pixel whose log filled with
+// translucent hits (ST_MORE) has its end beyond the record: it is queued (when
+// `end` or a sky map is asked for) for sr_ray_maps_resume_kernel, which writes
+// those maps for it. Reads the 16-byte record, 32 bytes per logged hit and ro
+// of a flat ray; the pixel state is not written.
+template <int V = 0>
+__global__ __launch_bounds__(256) void sr_ray_maps_kernel(const sr_dev_scene* __restrict__ sc,
+                                                          const float* __restrict__ segs,
+                                                          const uint32_t* __restrict__ arr, sr_dev_frame fr,
+                                                          const float* __restrict__ ps_base, size_t ps_n,
+                                                          sr_ray_map_ptrs m, size_t pitch, size_t frame_stride,
+                                                          int* __restrict__ list, int* __restrict__ count) {
+    const int vblock = (int)blockIdx.y * gridDim.x + blockIdx.x;  // frame f's tiles are rows f*gy ..
+    const int f = vblock / fr.tiles, block = vblock - f * fr.tiles;
+    Pix q;
+    if (!pixel_of(fr, block, threadIdx.x, q)) return;
+    const size_t id = (size_t)vblock * 256 + threadIdx.x;
+    Tex tx;
+    tx.bg = nullptr;
+    tx.arr = arr;
+    tx.opq = nullptr;
+    const float4 rec = *reinterpret_cast<const float4*>(ps_base + 4 * id);
+    const int w0 = __float_as_int(rec.x);
+    const int st = w0 & 7, nh = min((w0 >> 3) & 7, SR_PS_HITS);  // <= SR_PS_HITS written (memory safety)
+    const f3 rd = F3(rec.y, rec.z, rec.w);
+    const bool want_end = m.end || m.sky_dir || m.sky_uv;
+    const bool want_hit = m.hit_point || m.hit_normal || m.hit_view || m.hit_base || m.hit_step;
+
+    int code = PICK_NONE;  // ST_DONE: no ray
+    Hit first = no_hit();  // the first surface when it is an object's (code >= 0)
+    f3 first_view = F3(0.0f, 0.0f, 0.0f);
+    int first_step = -1;
+    bool ended = false;  // a hit of alpha exactly 1 so far
+    for (int j = 0; j < nh && !ended; j++) {
+        const float4* h4 = reinterpret_cast<const float4*>(ps_base + 4 * ps_n + (size_t)j * ps_n * 8 + id * 8);  // PS::hit
+        const float4 a = h4[0];
+        const int hw = __float_as_int(a.w);
+        const int key = (hw & 0xff) - PS_KEY_BIAS;
+        Hit h = no_hit();
+        h.slot = key >> 3;
+        h.face = key & 7;
+        h.p = F3(a.x, a.y, a.z);
+        if (j == 0) {
+            code = pick_code(h.slot);
+            if (!want_end && !(want_hit && code >= 0)) break;  // the id alone: sr_pick_kernel's 16 bytes
+        }
+        const float4 b = h4[1];
+        const f3 view = -F3(b.x, b.y, b.z);
+        if (j == 0 && code >= 0) {
+            first = h;
+            first_view = view;
+            first_step = (int)((unsigned)hw >> 8);
+            if (!want_end) break;
+        }
+        ended = hit_alpha(sc, fr, tx, h, view) == 1.0f;
+    }
+    int end = ended ? RAY_END_OPAQUE : RAY_END_NONE;
+    bool queued = false;
+    if (!ended) {
+        if (st == ST_BH) {
+            if (nh == 0) code = pick_code(SLOT_BH);
+            end = RAY_END_OPAQUE;
+        } else if (st == ST_HIT) {
+            end = RAY_END_OPAQUE;  // its last hit is opaque exactly (hit_opacity): never here
+        } else if (st == ST_BG) {
+            if (nh == 0) code = PICK_SKY;
+            end = RAY_END_SKY;
+        } else if (st == ST_FLAT && (nh == 0 || want_end)) {
+            // finish_ray's unbounded intersect; with no logged hit its winner is the first surface (pick_flat)
+            const size_t pl = (size_t)(PS_PLANES + PS_RO) * ps_n + id;  // PS::at
+            const f3 ro = F3(ps_base[pl], ps_base[pl + ps_n], ps_base[pl + 2 * ps_n]);
+            const Hit h = closest_hit_all(sc, segs, ro, rd, -1.0f);
+            float alpha = 0.0f;
+            bool back = false;
+            if (h.slot >= 0 && h.slot < SR_MAX_OBJECTS) {
+                const SurfaceMaterial g = surface_material(sc, fr, tx, h, -rd, false);
+                back = g.back;
+                alpha = back ? 0.0f : g.base.w;
+            } else if (h.slot != SLOT_NONE) {
+                alpha = hit_alpha(sc, fr, tx, h, -rd);
+            }
+            if (nh == 0) {
+                code = h.slot == SLOT_NONE || back ? PICK_SKY : pick_code(h.slot);
+                if (code >= 0) {
+                    first = h;
+                    first_view = -rd;
+                    first_step = (int)((unsigned)w0 >> 8);
+                }
+            }
+            end = alpha == 1.0f ? RAY_END_OPAQUE : RAY_END_SKY;
+        } else if (st == ST_MORE) {
+            queued = want_end;
+        }
+    }
+
+    const size_t e = ray_map_elem(q, f, pitch, frame_stride);
+    const float qn = __int_as_float(0x7fc00000);
+    if (m.id) m.id[e] = code;
+    if (queued) list[atomicAdd(count, 1)] = (int)id;
+    else if (want_end) put_ray_end(m, e, end, rd);
+    if (!want_hit) return;
+    const bool valid = code >= 0;
+    f4 base = F4(qn, qn, qn, qn);
+    f3 normal = F3(qn, qn, qn);
+    if (valid && first.slot < SR_MAX_OBJECTS && (m.hit_base || m.hit_normal)) {  // the bound: memory safety
+        const SurfaceMaterial g = surface_material(sc, fr, tx, first, first_view, m.hit_normal != nullptr);
+        base = g.base;
+        normal = g.normal;
+    }
+    if (m.hit_point) {
+        m.hit_point[3 * e + 0] = valid ? first.p.x : qn;
+        m.hit_point[3 * e + 1] = valid ? first.p.y : qn;
+        m.hit_point[3 * e + 2] = valid ? first.p.z : qn;
+    }
+    if (m.hit_normal) {
+        m.hit_normal[3 * e + 0] = normal.x;
+        m.hit_normal[3 * e + 1] = normal.y;
+        m.hit_normal[3 * e + 2] = normal.z;
+    }
+    if (m.hit_view) {
+        m.hit_view[3 * e + 0] = valid ? first_view.x : qn;
+        m.hit_view[3 * e + 1] = valid ? first_view.y : qn;
+        m.hit_view[3 * e + 2] = valid ? first_view.z : qn;
+    }
+    if (m.hit_base) {
+        m.hit_base[4 * e + 0] = base.x;
+        m.hit_base[4 * e + 1] = base.y;
+        m.hit_base[4 * e + 2] = base.z;
+        m.hit_base[4 * e + 3] = base.w;
+    }
+    if (m.hit_step) m.hit_step[e] = valid ? first_step : -1;
+}
+
+// The queued pixels (dense worklist, grid stride), walked on exactly as
+// sr_resume_kernel does: integrate<CULL, false, ...> rounds from the stored
+// state and, in place of shade(), its alpha, until a hit of alpha 1 or the
+// ray's end; then finish_ray's rule. Writes end, sky_dir and sky_uv of those
+// pixels; the pixel state is read and not written (RECORD = false logs nothing).
+template <bool CULL, bool TR = false>
+__global__ __launch_bounds__(SR_WG) void sr_ray_maps_resume_kernel(const sr_dev_scene* __restrict__ sc,
+                                                                 const float4* __restrict__ tbl,
+                                                                 const float* __restrict__ segs,
+                                                                 const uint32_t* __restrict__ arr, sr_dev_frame fr,
+                                                                 float* __restrict__ ps_base, size_t ps_n,
+                                                                 sr_ray_map_ptrs m, size_t pitch, size_t frame_stride,
+                                                                 const int* __restrict__ list,
+                                                                 const int* __restrict__ count) {
+    const int total = *count;
+    const PS ps{ps_base, ps_n};
+    Tex tx;
+    tx.bg = nullptr;
+    tx.arr = arr;
+    tx.opq = nullptr;
+    for (int w = blockIdx.x * SR_WG + threadIdx.x; w < total; w += gridDim.x * SR_WG) {
+        const int id = list[w];
+        const int f = (id >> 8) / fr.tiles;
+        Pix q;
+        pixel_of(fr, (id >> 8) - f * fr.tiles, id & 255, q);
+        Ray r;
+        const float4 rec = ps.get_rec(id);
+        r.ro = ps.get3(PS_RO, id);
+        r.rd = F3(rec.y, rec.z, rec.w);
+        r.nv = ps.get3(PS_NV, id);
+        r.tv = ps.get3(PS_TV, id);
+        r.u = ps.at(PS_U, id);
+        r.du = ps.at(PS_DU, id);
+        r.i = ps.geti(PS_I, id) + 1;
+        r.steps = (int)((unsigned)__float_as_int(rec.x) >> 8);
+        HitLog log{ps, 0};  // RECORD = false: nothing is logged
+        int end = RAY_END_NONE;
+        for (;;) {  // rounds: integrate to the next hit, its alpha, resume if not opaque
+            Hit hit = no_hit();
+            const int st = integrate<CULL, false, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, TR>(
+                sc, segs, tbl, fr, tx, r, hit, log);
+            if (st == ST_HIT) {
+                if (hit_alpha(sc, fr, tx, hit, -r.rd) == 1.0f) {  // frag:932
+                    end = RAY_END_OPAQUE;
+                    break;
+                }
+                r.i++;
+                continue;
+            }
+            if (st == ST_FLAT) {  // finish_ray
+                const Hit h = closest_hit_all(sc, segs, r.ro, r.rd, -1.0f);
+                end = h.slot != SLOT_NONE && hit_alpha(sc, fr, tx, h, -r.rd) == 1.0f ? RAY_END_OPAQUE : RAY_END_SKY;
+            } else if (st == ST_BG) {
+                end = RAY_END_SKY;
+            }
+            break;
+        }
+        // q is a pixel sr_ray_maps_kernel queued, so q.k < nrows and q.px < width
+        put_ray_end(m, ray_map_elem(q, f, pitch, frame_stride), end, r.rd);
+    }
+}
+
+extern "C" hipError_t sr_launch_ray_maps(const sr_dev_scene* sc, const float4* tbl, const float* segs,
+                                         const uint32_t* arr, const sr_dev_frame* fr, const float* ps, size_t ps_n,
+                                         const sr_ray_map_ptrs* maps, size_t pitch, size_t frame_stride, int* list,
+                                         int* count, hipStream_t stream) {
+    if (!fr || !maps) return hipErrorInvalidValue;
+    dim3 grid((fr->width + 15) / 16, (fr->nrows + 15) / 16);
+    if (grid.x == 0 || grid.y == 0) return hipSuccess;
+    const unsigned nblocks = grid.x * grid.y;
+    const unsigned B = (unsigned)fr->batch;
+    if (B < 1 || B > SR_MAX_BATCH || fr->tiles != (int)nblocks) return hipErrorInvalidValue;
+    if ((size_t)nblocks * B * 256 > ps_n || (size_t)nblocks * B * 256 > (size_t)INT32_MAX) return hipErrorInvalidValue;
+    if (!sc || !ps || !list || !count) return hipErrorInvalidValue;
+    const sr_ray_map_ptrs& m = *maps;
+    const bool want_end = m.end || m.sky_dir || m.sky_uv;
+    if (!want_end && !m.id && !m.hit_point && !m.hit_normal && !m.hit_view && !m.hit_base && !m.hit_step)
+        return hipErrorInvalidValue;
+    // the resume kernel's layout holds the scene's cylinders (sr_check_trace's rule)
+    if (want_end && (!tbl || (fr->cull != 0 && fr->num_budget_cyl > SR_NC_KERNEL))) return hipErrorInvalidValue;
+    const sr_trace_kind k = sr_select_trace(*fr);  // the resume kernel's rule for a frame that is no sequence's
+    decltype(&sr_ray_maps_resume_kernel<true>) kernel = nullptr;
+#define SR_X(cull, tr) \
+    if (k == sr_trace_kind{cull, tr}) kernel = sr_ray_maps_resume_kernel<cull, tr>;
+    SR_TRACE_KINDS(SR_X)
+#undef SR_X
+    if (!kernel) return hipErrorInvalidValue;
+    if (want_end) {
+        const hipError_t e = hipMemsetAsync(count, 0, sizeof(int), stream);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(sr_ray_maps_kernel<0>, dim3(grid.x, grid.y * B), dim3(256), 0, stream, sc, segs, arr, *fr, ps, ps_n,
+                       m, pitch, frame_stride, list, count);
+    if (!want_end) return hipGetLastError();
+    const unsigned tiles = nblocks * B < SR_RESUME_TILES ? nblocks * B : SR_RESUME_TILES;  // a grid-stride grid
+    hipLaunchKernelGGL(kernel, dim3(tiles * SR_WG_PER_TILE), dim3(SR_WG), 0, stream, sc, tbl, segs, arr, *fr,
+                       const_cast<float*>(ps), ps_n, m, pitch, frame_stride, list, count);
     return hipGetLastError();
 }

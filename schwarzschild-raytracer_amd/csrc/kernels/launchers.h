@@ -36,6 +36,13 @@ hipError_t sr_launch_reshade(const sr_dev_scene* sc, const float4* tbl, const fl
 // one object code per pixel from that state (sr_pick_map)
 hipError_t sr_launch_pick(const sr_dev_scene* sc, const float* segs, const sr_dev_frame* fr, const float* ps,
                           size_t ps_n, int32_t* out, size_t pitch, size_t frame_stride, hipStream_t stream);
+// the lens map and the first surface's G-buffer from that state (sr_ray_maps; sr.h "Ray maps"): the requested
+// maps (sr.h's struct, device pointers, any of them null), pitch and frame stride in pixels. list / count: the
+// context's resume worklist, cleared on the stream here and filled with the pixels whose hit log filled; they are
+// walked on by a second kernel (tbl: the step table) when `end` or a sky map is requested. ps is read only.
+hipError_t sr_launch_ray_maps(const sr_dev_scene* sc, const float4* tbl, const float* segs, const uint32_t* arr,
+                              const sr_dev_frame* fr, const float* ps, size_t ps_n, const sr_ray_map_ptrs* maps,
+                              size_t pitch, size_t frame_stride, int* list, int* count, hipStream_t stream);
 // caller-supplied rays, one lane each (sr_trace_rays; sr.h "Ray queries"): fr is a 1 x 1 frame's struct with
 // win_ok = 0, of which the schedule, the margins, the exclusions and the texture sizes are read; no pixel state
 hipError_t sr_launch_trace(const sr_dev_scene* sc, const float4* tbl, const float* segs, const uint32_t* bg,

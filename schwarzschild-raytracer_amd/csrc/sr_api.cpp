@@ -21,6 +21,7 @@
 #include "kernels/launchers.h"
 #include "kernels/shutter_div.h"
 #include "sr/projection.hpp"
+#include "sr/sky.hpp"
 #include "sr/sr.h"
 
 static_assert(sizeof(sr_pre::StepEntry) == sizeof(float4), "a step-table entry is one float4 load of the kernel");
@@ -1575,6 +1576,50 @@ int sr_pick_map(sr_ctx* c, int32_t* ids, size_t pitch, size_t frame_stride, sr_s
     return finish(c, sr_launch_pick(c->d_scene, c->d_segs, &fr, c->d_ps, c->ps_n, ids, pitch,
                                     fr.batch > 1 ? frame_stride : 0, s),
                   s);
+}
+
+// ---- ray maps (sr.h): the lens map and the first surface's G-buffer of the
+// retained frame. The worklist of the pixels to walk on is the context's own
+// resume queue (d_list, d_count: grown with the pixel state, released by
+// sr_destroy), free between the context's ordered launches.
+
+int sr_ray_maps(sr_ctx* c, const sr_ray_map_ptrs* m, size_t pitch, size_t frame_stride, sr_stream stream) {
+    if (!c || !m) return SR_E_INVALID;
+    if (!sr_can_reshade(c) || c->kept.ss > 1) return SR_E_NOT_READY;
+    const sr_ctx::Retained& k = c->kept;
+    const void* const ptrs[9] = {m->end,        m->id,       m->sky_dir,  m->sky_uv,  m->hit_point,
+                                 m->hit_normal, m->hit_view, m->hit_base, m->hit_step};
+    bool any = false;
+    for (const void* q : ptrs) {
+        if (((uintptr_t)q & 3) != 0) return SR_E_INVALID;
+        any = any || q != nullptr;
+    }
+    if (!any || pitch < (size_t)k.fr.width) return SR_E_INVALID;
+    if (k.fr.batch > 1 && frame_stride < pitch * (size_t)k.fr.nrows) return SR_E_INVALID;
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = enter_stream(c, s);
+    if (rc != SR_OK) return rc;
+    const float4* tbl = nullptr;  // the step table of the retained schedule, for the pixels walked on
+    rc = ensure_table(c, k.max_steps, k.max_revolutions, s, &tbl);
+    if (rc != SR_OK) return rc;
+    return finish(c, sr_launch_ray_maps(c->d_scene, tbl, c->d_segs, c->d_arr, &k.fr, c->d_ps, c->ps_n, m, pitch,
+                                        k.fr.batch > 1 ? frame_stride : 0, c->d_list, c->d_count, s),
+                  s);
+}
+
+namespace {
+struct HostAtan2 {
+    float operator()(float y, float x) const { return (float)std::atan2((double)y, (double)x); }
+};
+struct HostAsin {
+    float operator()(float x) const { return (float)std::asin((double)x); }
+};
+}  // namespace
+
+int sr_sky_uv(const float dir[3], float out_uv[2]) {
+    if (!dir || !out_uv) return SR_E_INVALID;
+    sr::sky_uv(dir[0], dir[1], dir[2], HostAtan2(), HostAsin(), out_uv);
+    return SR_OK;
 }
 
 // ---- ray queries (sr.h): caller-supplied rays through the current scene

@@ -617,6 +617,35 @@ class Renderer:
             m = m[frame]
         return int(m[int(y), int(x)].item())
 
+    # ---- ray maps (sr.h): the lens map and the first surface's G-buffer ----
+    def ray_maps(self, which=tuple(abi.RAY_MAPS), out=None, stream=None):
+        """sr_ray_maps: the maps named in `which` (keys of abi.RAY_MAPS) of the
+        retained launch -> a dict of tensors shaped like pick_map's with the
+        map's components last: [rows, W, n], or [B, rows, W, n] for a batch or
+        a block list (int32 for "end", "id" and "hit_step", float32 otherwise;
+        rows the launch left unwritten hold NaN, -1, RAY_END_NONE or PICK_NONE).
+        out: a dict of such tensors to write into instead. Asynchronous."""
+        t = self.torch
+        which = tuple(which)
+        if not which or any(k not in abi.RAY_MAPS for k in which):
+            raise ValueError(f"ray_maps: maps are {tuple(abi.RAY_MAPS)}, at least one")
+        w, rows, frames, _ = self._retained_shape("sr_ray_maps")
+        fill = {"end": abi.RAY_END_NONE, "id": abi.PICK_NONE, "hit_step": -1}
+        maps, ptrs = {}, abi.RayMapPtrs()
+        for key in which:
+            n, dtype = abi.RAY_MAPS[key]
+            dt = getattr(t, dtype)
+            if out is not None and key in out:
+                m = out[key]
+                assert m.is_contiguous() and m.dtype == dt and m.numel() >= frames * rows * w * n
+            else:
+                shape = (rows, w, n) if frames == 1 else (frames, rows, w, n)
+                m = t.full(shape, fill.get(key, float("nan")), dtype=dt, device=self.tdev)
+            maps[key] = m
+            setattr(ptrs, key, m.data_ptr())
+        abi.check(self.lib.sr_ray_maps(self.ctx, C.byref(ptrs), w, rows * w, self._stream(stream)), "sr_ray_maps")
+        return maps
+
     # ---- ray queries (sr.h): caller-supplied rays through the current scene ----
     def trace_rays(self, origins, dirs, params: abi.Params, rgba32: bool = False, rgba8: bool = True,
                    steps: bool = False, ids: bool = False, stream=None):
