@@ -10,13 +10,13 @@
 
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <new>
 #include <tuple>
 #include <utility>
 #include <vector>
 
 #include "device_scene.h"
+#include "host/device_cache.h"
 #include "host/precompute.h"
 #include "kernels/launchers.h"
 #include "kernels/shutter_div.h"
@@ -28,16 +28,16 @@ static_assert(sizeof(sr_pre::StepEntry) == sizeof(float4), "a step-table entry i
 
 namespace {
 
-struct Table {
-    float4* dev = nullptr;
-    std::vector<sr_pre::StepEntry> host;  // source of the stream-ordered upload, kept until the entry goes
-    uint64_t used = 0;
+// A grow-on-demand scratch buffer of the context (grow, drop), `n` elements:
+// the pixel pipeline's SR_PS_FIELDS planes of floats per pixel id, resume
+// worklist and counter pair (geodesic.hip); the sample frame of a supersampled
+// launch (resolve.hip); adaptive supersampling's flagged output tiles (bytes)
+// and the sparse launch's code list (adaptive.hip)
+struct Scratch {
+    void* p = nullptr;
+    size_t n = 0;
 };
-
-// Device caches of a context (step tables, launch orders, block lists) hold at
-// most this many entries each; the least recently used goes, its buffers
-// freed in stream order after the context's in-flight frames.
-constexpr size_t kCacheEntries = 8;
+enum { kPs, kList, kCount, kSs, kAmask, kAcodes, kScratches };
 
 }  // namespace
 
@@ -57,36 +57,20 @@ struct sr_ctx {
     float xc_uf = NAN, xc_dphi = NAN;
     float xc_need[SR_MAX_BUDGET];
     float xc_peri[SR_MAX_BUDGET];
-    // pixel pipeline scratch (geodesic.hip): SR_PS_FIELDS planes of ps_n floats,
-    // the resume worklist and its counter; grown on demand, reused per frame.
-    // Renders on one context are ordered on its stream(s) by the caller.
-    float* d_ps = nullptr;
-    int* d_list = nullptr;
-    int* d_count = nullptr;
-    size_t ps_n = 0;
-    // workgroup-tile launch order (costliest first) and per-tile cost of the
-    // last frame, one pair per grid shape (geodesic.hip order_tiles): kept
-    // for the context's lifetime, so a shape change never frees a buffer an
-    // in-flight frame still reads
-    struct Order {
-        int* order = nullptr;
-        int* cost = nullptr;
-        std::vector<int> host;  // source of the stream-ordered upload
-        uint64_t used = 0;
-    };
-    // (gx, gy, split_tiles, split_log2, block list, projection): a block
-    // list's tiles have their own costs; the list is its device copy, one per
-    // distinct content. A projection's frames have their own costs too: a
-    // pinhole frame never runs in an order learned from a panorama
-    std::map<std::tuple<int, int, int, int, const int*, int>, Order> orders;
-    // device copies of the block lists of sr_render_block_list, by content
-    // (the key is the upload's source)
-    struct BlockList {
-        int* dev = nullptr;
-        uint64_t used = 0;
-    };
-    std::map<std::vector<int>, BlockList> block_lists;
-    uint64_t tick = 0;  // LRU clock of the caches
+    // reused per frame (renders on one context are ordered on its stream(s)
+    // by the caller); ps_n: the pixel ids the pixel state holds
+    Scratch scratch[kScratches];
+    size_t ps_n() const { return scratch[kList].n; }
+    float* d_ps() const { return static_cast<float*>(scratch[kPs].p); }
+    int* d_list() const { return static_cast<int*>(scratch[kList].p); }
+    int* d_count() const { return static_cast<int*>(scratch[kCount].p); }
+    uint8_t* d_ss() const { return static_cast<uint8_t*>(scratch[kSs].p); }
+    uint8_t* d_amask() const { return static_cast<uint8_t*>(scratch[kAmask].p); }
+    int* d_acodes() const { return static_cast<int*>(scratch[kAcodes].p); }
+    // step tables, the sequence's exclusion tables, launch orders, block lists
+    // and the launch codes of the context's last frame (its next frame's order).
+    // An entry goes in stream order or, with the sequence, after a wait.
+    sr_cache::Caches caches;
     // synchronous uploads (sr_set_*) run on this non-blocking stream, never
     // on the null stream (which would wait for other contexts' work)
     hipStream_t upload = nullptr;
@@ -94,8 +78,6 @@ struct sr_ctx {
     int split_tiles = 0, split_log2 = 4, split_min_steps = 1;
     int fast_unroll = SR_FAST_UNROLL_DEFAULT;  // sr_set_latency_mode: 2
     int projection = SR_PROJECTION_RECTILINEAR;  // sr_set_projection
-    const int* last_order = nullptr;  // the launch codes of the context's last frame (its next frame's order)
-    size_t last_slots = 0;
     // the stream of the context's last launch: a context is used from one
     // stream, so waiting for it waits for every frame that
     // may still read the context's buffers, and for nothing else on the device
@@ -113,23 +95,11 @@ struct sr_ctx {
     // launch on its stream before the integrate kernel reads it (geodesic.hip
     // sr_start_table_kernel); nothing in it outlives the launch
     sr_dev_start* d_start = nullptr;
-    // the sample frame of a supersampled launch (sr_render_ss,
-    // sr_render_block_list_ss; resolve.hip reads it): grown on demand, reused
-    uint8_t* d_ss = nullptr;
-    size_t ss_bytes = 0;
-    // adaptive supersampling (sr_render_adaptive; adaptive.hip): the flagged
-    // output tiles (bytes) and the sparse launch's code list (one int per
-    // sample tile); grown on demand, reused
-    uint8_t* d_amask = nullptr;
-    size_t amask_n = 0;
-    int* d_acodes = nullptr;
-    size_t acodes_n = 0;
     // optional per-kernel timing: 4 events per frame (before integrate, after
     // integrate, after shade, after resume), a ring of `timing_cap` frames
     std::vector<hipEvent_t> tev;
     int timing_cap = 0;
     int timing_n = 0;
-    std::map<std::pair<int, int>, Table> tables;  // (max_steps, max_revolutions) -> table
     // the retained frame (sr.h "Retained frames"): what the pixel state holds
     // since the last launch, for sr_reshade and sr_pick_map. fr is the
     // launch's own frame struct (a supersampled launch's: the sample frame's);
@@ -150,16 +120,6 @@ struct sr_ctx {
     // again); a state of its own beside d_scene / h_scene
     sr_dev_scene* d_seq = nullptr;
     std::vector<sr_dev_scene> h_seq;
-    // the sequence's low-energy exclusions per (u_f, step angle) (their bits):
-    // xlow_need, then xperi_e, of every scene, as sr_launch_geodesic_seq reads
-    // them. Frames in flight keep the table they were launched with: an entry
-    // goes in stream order (evict_lru) or, with the sequence, after a wait.
-    struct XTab {
-        float* dev = nullptr;
-        std::vector<float> host;  // source of the stream-ordered upload
-        uint64_t used = 0;
-    };
-    std::map<std::pair<uint32_t, uint32_t>, XTab> xtabs;
 };
 
 namespace {
@@ -174,87 +134,38 @@ void release(sr_ctx* ctx, void* p, hipStream_t s) {
     if (p && !hip_ok(hipFreeAsync(p, ctx->launched ? ctx->last_stream : s))) ctx->free_errors++;
 }
 
-// LRU eviction down to kCacheEntries - 1 entries (one is about to be added).
-template <class Map, class Free>
-void evict_lru(sr_ctx* ctx, Map& m, Free&& free_entry) {
-    while (m.size() >= kCacheEntries) {
-        auto victim = m.begin();
-        for (auto it = m.begin(); it != m.end(); ++it)
-            if (it->second.used < victim->second.used) victim = it;
-        free_entry(victim->second);
-        m.erase(victim);
+// The caches' device (host/device_cache.h); the frees are release()'s
+struct HipDevice {
+    sr_ctx* ctx;
+    bool alloc(void** p, size_t bytes, void* s) { return hip_ok(hipMallocAsync(p, bytes, hipStream_t(s))); }
+    bool upload(void* dst, const void* src, size_t bytes, void* s) {
+        return hip_ok(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, hipStream_t(s)));
     }
-}
+    bool zero(void* dst, size_t bytes, void* s) { return hip_ok(hipMemsetAsync(dst, 0, bytes, hipStream_t(s))); }
+    void free(void* p, void* s) { release(ctx, p, hipStream_t(s)); }
+};
 
 int ensure_table(sr_ctx* ctx, int max_steps, int max_revs, hipStream_t s, const float4** out) {
-    auto key = std::make_pair(max_steps, max_revs);
-    auto it = ctx->tables.find(key);
-    if (it != ctx->tables.end()) {
-        it->second.used = ++ctx->tick;
-        *out = it->second.dev;
-        return SR_OK;
-    }
-    evict_lru(ctx, ctx->tables, [&](Table& t) { release(ctx, t.dev, ctx->last_stream); });
-    Table& t = ctx->tables[key];
-    t.host = sr_pre::step_table(max_steps, max_revs);
-    t.used = ++ctx->tick;
-    // stream-ordered: allocated and filled on the caller's stream, ahead of
-    // the launch that reads it (no device-wide synchronisation)
-    if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&t.dev), t.host.size() * sizeof(float4), s))) {
-        ctx->tables.erase(key);
-        return SR_E_NOMEM;
-    }
-    if (!hip_ok(hipMemcpyAsync(t.dev, t.host.data(), t.host.size() * sizeof(float4), hipMemcpyHostToDevice, s))) {
-        release(ctx, t.dev, s);
-        ctx->tables.erase(key);
-        return SR_E_HIP;
-    }
-    *out = t.dev;
-    return SR_OK;
+    return ctx->caches.table(
+        HipDevice{ctx}, {max_steps, max_revs}, s, ctx->last_stream,
+        [&](std::vector<sr_pre::StepEntry>& t) { t = sr_pre::step_table(max_steps, max_revs); }, out);
 }
 
 // Floats per scene of an exclusion table (geodesic.hip SR_XTAB_FLOATS)
 constexpr size_t kXTabFloats = 2 * SR_MAX_BUDGET;
 
-// The sequence's exclusion table for a launch's (u_f, step angle): computed
-// and uploaded once per pair on the caller's stream, like a step table.
+// The sequence's exclusion table for a launch's (u_f, step angle): xlow_need,
+// then xperi_e, of every scene, as sr_launch_geodesic_seq reads them
 int ensure_xtab(sr_ctx* ctx, float u_f, float max_dphi, hipStream_t s, const float** out) {
-    uint32_t ku, kd;
-    std::memcpy(&ku, &u_f, sizeof ku);
-    std::memcpy(&kd, &max_dphi, sizeof kd);
-    const auto key = std::make_pair(ku, kd);
-    auto it = ctx->xtabs.find(key);
-    if (it != ctx->xtabs.end()) {
-        it->second.used = ++ctx->tick;
-        *out = it->second.dev;
-        return SR_OK;
-    }
-    evict_lru(ctx, ctx->xtabs, [&](sr_ctx::XTab& t) { release(ctx, t.dev, ctx->last_stream); });
-    sr_ctx::XTab& t = ctx->xtabs[key];
-    t.host.resize(ctx->h_seq.size() * kXTabFloats);
-    for (size_t k = 0; k < ctx->h_seq.size(); k++)
-        sr_pre::low_energy_exclusions(ctx->h_seq[k], u_f, max_dphi, &t.host[k * kXTabFloats],
-                                      &t.host[k * kXTabFloats + SR_MAX_BUDGET]);
-    t.used = ++ctx->tick;
-    const size_t bytes = t.host.size() * sizeof(float);
-    if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&t.dev), bytes, s))) {
-        ctx->xtabs.erase(key);
-        return SR_E_NOMEM;
-    }
-    if (!hip_ok(hipMemcpyAsync(t.dev, t.host.data(), bytes, hipMemcpyHostToDevice, s))) {
-        release(ctx, t.dev, s);
-        ctx->xtabs.erase(key);
-        return SR_E_HIP;
-    }
-    *out = t.dev;
-    return SR_OK;
-}
-
-// Drops every exclusion table (the sequence they were computed from goes);
-// the context's frames are done (wait_ctx), the frees are stream-ordered all the same
-void drop_xtabs(sr_ctx* ctx) {
-    for (auto& kv : ctx->xtabs) release(ctx, kv.second.dev, ctx->upload);
-    ctx->xtabs.clear();
+    return ctx->caches.xtab(
+        HipDevice{ctx}, u_f, max_dphi, s, ctx->last_stream,
+        [&](std::vector<float>& t) {
+            t.resize(ctx->h_seq.size() * kXTabFloats);
+            for (size_t k = 0; k < ctx->h_seq.size(); k++)
+                sr_pre::low_energy_exclusions(ctx->h_seq[k], u_f, max_dphi, &t[k * kXTabFloats],
+                                              &t[k * kXTabFloats + SR_MAX_BUDGET]);
+        },
+        out);
 }
 
 // Synchronous upload of host bytes into a fresh device buffer on the
@@ -288,53 +199,43 @@ bool wait_ctx(sr_ctx* ctx) {
     return hip_ok(hipStreamSynchronize(ctx->last_stream));
 }
 
+void drop(sr_ctx* ctx, Scratch& b, hipStream_t s) {
+    release(ctx, b.p, s);
+    b = Scratch();
+}
+
+// Grows a scratch buffer to `want` elements of `size` bytes in stream order:
+// the old buffer is freed after the context's in-flight frames, the new one
+// allocated on the caller's stream ahead of the launch (no host wait, no
+// device-wide synchronisation); its contents are not kept.
+int grow(sr_ctx* ctx, int which, size_t want, size_t size, hipStream_t s) {
+    Scratch& b = ctx->scratch[which];
+    if (want <= b.n) return SR_OK;
+    drop(ctx, b, s);
+    if (!hip_ok(hipMallocAsync(&b.p, want * size, s))) {
+        b.p = nullptr;
+        return SR_E_NOMEM;
+    }
+    b.n = want;
+    return SR_OK;
+}
+
 void free_pixel_state(sr_ctx* ctx, hipStream_t s) {
     ctx->kept.valid = false;  // the retained rays go with the planes
-    release(ctx, ctx->d_ps, s);
-    release(ctx, ctx->d_list, s);
-    release(ctx, ctx->d_count, s);
-    ctx->d_ps = nullptr;
-    ctx->d_list = nullptr;
-    ctx->d_count = nullptr;
-    ctx->ps_n = 0;
+    for (int b : {kPs, kList, kCount}) drop(ctx, ctx->scratch[b], s);
 }
 
-// Grows the pixel-state planes in stream order: the old buffers are freed
-// after the context's in-flight frames, the new ones allocated and cleared
-// on the caller's stream ahead of the launch (no host wait, no device-wide
-// synchronisation).
+// Grows the pixel state to n pixel ids
 int ensure_pixel_state(sr_ctx* ctx, size_t n, hipStream_t s) {
-    if (n <= ctx->ps_n) return SR_OK;
+    if (n <= ctx->ps_n()) return SR_OK;
     free_pixel_state(ctx, s);
-    if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&ctx->d_ps), n * SR_PS_FIELDS * sizeof(float), s)) ||
-        !hip_ok(hipMallocAsync(reinterpret_cast<void**>(&ctx->d_list), n * sizeof(int), s)) ||
-        !hip_ok(hipMallocAsync(reinterpret_cast<void**>(&ctx->d_count), 2 * sizeof(int), s))) {
-        free_pixel_state(ctx, s);
-        return SR_E_NOMEM;
-    }
+    int rc = grow(ctx, kPs, n * SR_PS_FIELDS, sizeof(float), s);
+    if (rc == SR_OK) rc = grow(ctx, kList, n, sizeof(int), s);
+    if (rc == SR_OK) rc = grow(ctx, kCount, 2, sizeof(int), s);
     // [0]: the shade kernel's resume queue
-    if (!hip_ok(hipMemsetAsync(ctx->d_count, 0, 2 * sizeof(int), s))) {
-        free_pixel_state(ctx, s);
-        return SR_E_HIP;
-    }
-    ctx->ps_n = n;
-    return SR_OK;
-}
-
-// Grows one scratch buffer (the sample frame, the adaptive tile mask and code
-// list) to `want` elements the same way; its contents are not kept.
-template <class T>
-int grow(sr_ctx* ctx, T*& p, size_t& have, size_t want, hipStream_t s) {
-    if (want <= have) return SR_OK;
-    release(ctx, p, s);
-    p = nullptr;
-    have = 0;
-    if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&p), want * sizeof(T), s))) {
-        p = nullptr;
-        return SR_E_NOMEM;
-    }
-    have = want;
-    return SR_OK;
+    if (rc == SR_OK) rc = status(hipMemsetAsync(ctx->d_count(), 0, 2 * sizeof(int), s));
+    if (rc != SR_OK) free_pixel_state(ctx, s);
+    return rc;
 }
 
 // Entries of a launch order over n tiles: the split grid adds (64 >> log2) - 1
@@ -344,53 +245,19 @@ size_t launch_slots(const sr_ctx* ctx, size_t n) {
     return n + (size_t)((64 >> (split ? ctx->split_log2 : 6)) - 1) * (size_t)split;
 }
 
-void drop_order(sr_ctx* ctx, sr_ctx::Order& o) {
-    if (ctx->last_order == o.order) {
-        ctx->last_order = nullptr;
-        ctx->last_slots = 0;
-    }
-    release(ctx, o.order, ctx->last_stream);
-    release(ctx, o.cost, ctx->last_stream);
-}
-
 // Launch order for a grid shape: tiles nearest the frame centre first (where
 // the black hole usually is) until a frame has measured the costs. One
 // buffer pair per shape and split setting, allocated on first use. Entries
 // are launch codes (geodesic.hip order_tiles): tile << 8 for a whole
-// tile, -1 for the split grid's slots no tile uses yet.
-int ensure_order(sr_ctx* ctx, int gx, int gy, const int* list, hipStream_t s, int** order, int** cost) {
+// tile, -1 for the split grid's slots no tile uses yet. out[0]: the order,
+// out[1]: the tiles' costs.
+int ensure_order(sr_ctx* ctx, int gx, int gy, const int* list, hipStream_t s, int** out) {
     const int split = ctx->split_tiles;
-    const auto key = std::make_tuple(gx, gy, split, split ? ctx->split_log2 : 0, list, ctx->projection);
-    auto it = ctx->orders.find(key);
-    if (it != ctx->orders.end()) {
-        it->second.used = ++ctx->tick;
-        *order = it->second.order;
-        *cost = it->second.cost;
-        return SR_OK;
-    }
     const size_t n = (size_t)gx * gy;
-    const size_t slots = launch_slots(ctx, n);
-    evict_lru(ctx, ctx->orders, [&](sr_ctx::Order& o) { drop_order(ctx, o); });
-    sr_ctx::Order& o = ctx->orders[key];
-    o.host = sr_pre::centre_first_order(gx, gy, slots);
-    o.used = ++ctx->tick;
-    // stream-ordered, on the caller's stream ahead of the launch
-    if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&o.order), slots * sizeof(int), s)) ||
-        !hip_ok(hipMallocAsync(reinterpret_cast<void**>(&o.cost), n * sizeof(int), s))) {
-        release(ctx, o.order, s);
-        ctx->orders.erase(key);
-        return SR_E_NOMEM;
-    }
-    if (!hip_ok(hipMemcpyAsync(o.order, o.host.data(), slots * sizeof(int), hipMemcpyHostToDevice, s)) ||
-        !hip_ok(hipMemsetAsync(o.cost, 0, n * sizeof(int), s))) {
-        release(ctx, o.order, s);
-        release(ctx, o.cost, s);
-        ctx->orders.erase(key);
-        return SR_E_HIP;
-    }
-    *order = o.order;
-    *cost = o.cost;
-    return SR_OK;
+    return ctx->caches.order(
+        HipDevice{ctx}, std::make_tuple(gx, gy, split, split ? ctx->split_log2 : 0, list, ctx->projection),
+        n * sizeof(int), s, ctx->last_stream,
+        [&](std::vector<int>& o) { o = sr_pre::centre_first_order(gx, gy, launch_slots(ctx, n)); }, out);
 }
 
 // The block-list paths' own rejections: the arguments, the rows of the launch
@@ -405,47 +272,15 @@ int check_block_list(const sr_ctx* c, const void* out, const int* blocks, int n_
     return SR_OK;
 }
 
-// The device copy of a block list (sr_render_block_list), uploaded once per
-// distinct list on the caller's stream and kept for the context's lifetime (a
-// rank's balanced list does not change between frames).
-int ensure_block_list(sr_ctx* ctx, const int* blocks, int n, sr_stream stream, const int** dev) {
-    if (!hip_ok(hipSetDevice(ctx->device))) return SR_E_HIP;
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    std::vector<int> key(blocks, blocks + n);
-    auto it = ctx->block_lists.find(key);
-    if (it != ctx->block_lists.end()) {
-        it->second.used = ++ctx->tick;
-        *dev = it->second.dev;
-        return SR_OK;
-    }
-    // an evicted list's launch orders go with it (they are keyed by its device copy)
-    evict_lru(ctx, ctx->block_lists, [&](sr_ctx::BlockList& b) {
-        for (auto o = ctx->orders.begin(); o != ctx->orders.end();) {
-            if (std::get<4>(o->first) == b.dev) {
-                drop_order(ctx, o->second);
-                o = ctx->orders.erase(o);
-            } else {
-                ++o;
-            }
-        }
-        if (ctx->kept.fr.block_list == b.dev || ctx->kept.d_blocks == b.dev) ctx->kept.valid = false;
-        release(ctx, b.dev, ctx->last_stream);
-    });
-    // the map's key is the source of the stream-ordered upload: it lives as long as the entry
-    auto ins = ctx->block_lists.emplace(std::move(key), sr_ctx::BlockList{});
-    sr_ctx::BlockList& b = ins.first->second;
-    b.used = ++ctx->tick;
-    if (!hip_ok(hipMallocAsync(reinterpret_cast<void**>(&b.dev), (size_t)n * sizeof(int), s))) {
-        ctx->block_lists.erase(ins.first);
-        return SR_E_NOMEM;
-    }
-    if (!hip_ok(hipMemcpyAsync(b.dev, ins.first->first.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s))) {
-        release(ctx, b.dev, s);
-        ctx->block_lists.erase(ins.first);
-        return SR_E_HIP;
-    }
-    *dev = b.dev;
-    return SR_OK;
+// The device copy of a block list, uploaded once per distinct list (a rank's
+// balanced list does not change between frames); after enter_stream, like every ensure_*.
+int ensure_block_list(sr_ctx* ctx, const int* blocks, int n, hipStream_t s, const int** dev) {
+    const sr_ctx::Retained& k = ctx->kept;
+    const int* const kept[2] = {k.valid ? k.fr.block_list : nullptr, k.valid ? k.d_blocks : nullptr};
+    bool gone = false;
+    const int rc = ctx->caches.block_list(HipDevice{ctx}, blocks, n, s, ctx->last_stream, kept, &gone, dev);
+    if (gone) ctx->kept.valid = false;
+    return rc;
 }
 
 // Makes `s` the context's launch stream: ordered after the launches on the
@@ -486,6 +321,9 @@ struct Launch {
     // rows: output row k renders frame row row_base + (k / block_rows) *
     // block_stride + k % block_rows, or the block list's (device_scene.h)
     int nrows = 0, row_base = 0, block_rows = 1, block_stride = 0;
+    // the caller's list, and its device copy once resolved (ensure_block_list: after every rejection)
+    const int* blocks = nullptr;
+    int n_blocks = 0;
     const int* d_block_list = nullptr;
     // output
     uint8_t* out = nullptr;
@@ -534,12 +372,13 @@ struct Launch {
         block_stride = block_step * rows_per_block;
         return *this;
     }
-    // the blocks of a device list (ensure_block_list), -1 entries unwritten
-    Launch& block_list(const int* d_list, int n_blocks, int rows_per_block) {
-        nrows = n_blocks * rows_per_block;
+    // the blocks of a list, -1 entries unwritten
+    Launch& block_list(const int* list, int n, int rows_per_block) {
+        nrows = n * rows_per_block;
         row_base = 0;
         block_rows = block_stride = rows_per_block;
-        d_block_list = d_list;
+        blocks = list;
+        n_blocks = n;
         return *this;
     }
     Launch& sequence(int first_scene) {
@@ -564,6 +403,25 @@ int check_frames(const sr_ctx* c, const sr_camera* cams, int n_frames, const sr_
     if (seq_first != -1 && (seq_first < 0 || (size_t)seq_first + (size_t)n_frames > c->h_seq.size())) return SR_E_INVALID;
     if (n_frames > SR_MAX_BATCH) return SR_E_CAPACITY;
     return sr_pre::check_frame_args(cams, p, width, height);
+}
+
+// What a frame struct takes from the context: its scene's low-energy
+// exclusions per (u_f, step angle) (NaN: sr_set_scene's reset) and the texture sizes
+void context_into_frame(sr_ctx* ctx, bool own_scene, sr_dev_frame& fr) {
+    if (own_scene) {
+        if (!(ctx->xc_uf == fr.u_f && ctx->xc_dphi == fr.max_dphi)) {
+            sr_pre::low_energy_exclusions(ctx->h_scene, fr.u_f, fr.max_dphi, ctx->xc_need, ctx->xc_peri);
+            ctx->xc_uf = fr.u_f;
+            ctx->xc_dphi = fr.max_dphi;
+        }
+        std::memcpy(fr.xlow_need, ctx->xc_need, sizeof fr.xlow_need);
+        std::memcpy(fr.xperi_e, ctx->xc_peri, sizeof fr.xperi_e);
+    }
+    fr.bg_w = ctx->bg_w;
+    fr.bg_h = ctx->bg_h;
+    fr.arr_w = ctx->arr_w;
+    fr.arr_h = ctx->arr_h;
+    fr.arr_layers = ctx->arr_layers;
 }
 
 // A launch's frame struct: every rejection, then the constants (precompute.cpp
@@ -599,20 +457,8 @@ int build_frame(sr_ctx* ctx, const Launch& r, sr_dev_frame& fr) {
             if (sc.num_budget > fr.num_budget) fr.num_budget = sc.num_budget;
             if (cyl > fr.num_budget_cyl) fr.num_budget_cyl = cyl;
         }
-    } else {
-        if (!(ctx->xc_uf == fr.u_f && ctx->xc_dphi == fr.max_dphi)) {
-            sr_pre::low_energy_exclusions(ctx->h_scene, fr.u_f, fr.max_dphi, ctx->xc_need, ctx->xc_peri);
-            ctx->xc_uf = fr.u_f;
-            ctx->xc_dphi = fr.max_dphi;
-        }
-        std::memcpy(fr.xlow_need, ctx->xc_need, sizeof fr.xlow_need);
-        std::memcpy(fr.xperi_e, ctx->xc_peri, sizeof fr.xperi_e);
     }
-    fr.bg_w = ctx->bg_w;
-    fr.bg_h = ctx->bg_h;
-    fr.arr_w = ctx->arr_w;
-    fr.arr_h = ctx->arr_h;
-    fr.arr_layers = ctx->arr_layers;
+    context_into_frame(ctx, !seq, fr);
     fr.split_tiles = r.d_codes ? 0 : ctx->split_tiles;
     fr.split_log2 = ctx->split_log2;
     fr.split_min_steps = ctx->split_min_steps;
@@ -641,16 +487,19 @@ int launch(sr_ctx* ctx, const Launch& r) {
     if (rc != SR_OK) return rc;
     rc = ensure_pixel_state(ctx, (size_t)fr.tiles * (size_t)r.n_frames * 256, s);
     if (rc != SR_OK) return rc;
-    int* order = nullptr;
-    int* cost = nullptr;
+    if (r.blocks && !fr.block_list) {  // launch_ss and launch_sub_frames resolved theirs
+        rc = ensure_block_list(ctx, r.blocks, r.n_blocks, s, &fr.block_list);
+        if (rc != SR_OK) return rc;
+    }
+    int* order[2] = {};  // and the tiles' costs
     if (r.d_codes) {
-        order = r.d_codes;  // no cost feedback: order_tiles does not run, last_order stays the plain frame's
+        order[0] = r.d_codes;  // no cost feedback: order_tiles does not run, last_order stays the plain frame's
     } else if (r.nrows > 0) {
         const int gx = (r.width + 15) / 16, gy = (r.nrows + 15) / 16;
-        rc = ensure_order(ctx, gx, gy, r.d_block_list, s, &order, &cost);
+        rc = ensure_order(ctx, gx, gy, fr.block_list, s, order);
         if (rc != SR_OK) return rc;
-        ctx->last_order = order;
-        ctx->last_slots = launch_slots(ctx, (size_t)gx * (size_t)gy);
+        ctx->caches.last_order = order[0];
+        ctx->caches.last_slots = launch_slots(ctx, (size_t)gx * (size_t)gy);
     }
     const bool seq = r.seq_first != -1;
     const float* xtab = nullptr;
@@ -662,11 +511,11 @@ int launch(sr_ctx* ctx, const Launch& r) {
     const hipError_t e =
         seq ? sr_launch_geodesic_seq(ctx->d_seq + r.seq_first, xtab + (size_t)r.seq_first * kXTabFloats, tbl, ctx->d_segs,
                                      ctx->d_bg, ctx->d_arr, ctx->d_opq, &fr, r.out, r.pitch, r.dbg_rgba, r.dbg_steps,
-                                     ctx->d_ps, ctx->ps_n, ctx->d_list, ctx->d_count, order, cost, ctx->d_diag,
-                                     ctx->d_start, ev4, s)
+                                     ctx->d_ps(), ctx->ps_n(), ctx->d_list(), ctx->d_count(), order[0], order[1],
+                                     ctx->d_diag, ctx->d_start, ev4, s)
             : sr_launch_geodesic(ctx->d_scene, tbl, ctx->d_segs, ctx->d_bg, ctx->d_arr, ctx->d_opq, &fr, r.out, r.pitch,
-                                 r.dbg_rgba, r.dbg_steps, ctx->d_ps, ctx->ps_n, ctx->d_list, ctx->d_count, order, cost,
-                                 ctx->d_diag, ctx->d_start, ev4, s);
+                                 r.dbg_rgba, r.dbg_steps, ctx->d_ps(), ctx->ps_n(), ctx->d_list(), ctx->d_count(), order[0],
+                                 order[1], ctx->d_diag, ctx->d_start, ev4, s);
     rc = finish(ctx, e, s);
     // the retained frame: whole launches of at least one row (a sparse launch
     // holds only its tiles' rays, sr_wave_costs writes no pixels; the callers
@@ -683,19 +532,53 @@ int launch(sr_ctx* ctx, const Launch& r) {
     return rc;
 }
 
+// The launch `r` into the context's sample scratch (`bytes` of it: rows of `pitch` bytes, frames
+// `frame_stride` apart), for a post-kernel of the caller's, which reads the block list's device
+// copy too. Every argument was checked by the caller and check_frames.
+int launch_into_scratch(sr_ctx* c, Launch& r, size_t bytes, size_t pitch, size_t frame_stride) {
+    const hipStream_t s = reinterpret_cast<hipStream_t>(r.stream);
+    int rc = enter_stream(c, s);
+    if (rc == SR_OK) rc = grow(c, kSs, bytes, 1, s);
+    if (rc == SR_OK && r.blocks) rc = ensure_block_list(c, r.blocks, r.n_blocks, s, &r.d_block_list);
+    if (rc != SR_OK) return rc;
+    return launch(c, r.into(c->d_ss(), pitch, frame_stride));
+}
+
+// The sub-frames of a phase launch (sr_render_accumulate, the shutter entry
+// points) into the sample scratch, at r.pitch and r.frame_stride. No retained
+// frame: the sub-frames are not a caller's output.
+int launch_sub_frames(sr_ctx* c, Launch& r) {
+    const size_t ipitch = (size_t)r.width * 4, istride = ipitch * (size_t)r.nrows;
+    const int rc = launch_into_scratch(c, r, istride * (size_t)r.n_frames, ipitch, istride);
+    c->kept.valid = false;
+    return rc;
+}
+
+// The sub-frames of `r`, then their sum into (reset: over) the caller's accumulator
+int accumulate_sub_frames(sr_ctx* c, Launch& r, int reset, uint16_t* accum, size_t accum_pitch) {
+    c->kept.valid = false;
+    if (r.nrows == 0) return SR_OK;  // no rows: nothing is written
+    const int rc = launch_sub_frames(c, r);
+    if (rc != SR_OK) return rc;
+    // again at the end of the whole: a launch on another stream waits for the add too
+    const hipStream_t s = reinterpret_cast<hipStream_t>(r.stream);
+    return finish(c, sr_accum_add_device(c->d_ss(), r.pitch, r.frame_stride, r.n_frames, r.width, r.nrows, reset ? 1 : 0,
+                                         accum, accum_pitch, s),
+                  s);
+}
+
 // ---- supersampling: the sample frame is an ordinary launch of the (ss x
 // width) x (ss x height) frame into the context's sample scratch, resolved
 // to the caller's buffer by resolve.hip on the same stream.
-// `o` is the launch in output pixels (one band, or a block list's slots);
-// every argument was checked by the caller and check_frames.
+// `o` is the launch in output pixels (one band, or a block list's slots).
 int launch_ss(sr_ctx* c, const Launch& o, int ss) {
+    if (o.nrows == 0) {  // no rows: nothing is written
+        c->kept.valid = false;
+        return SR_OK;
+    }
     const hipStream_t s = reinterpret_cast<hipStream_t>(o.stream);
-    int rc = enter_stream(c, s);
-    if (rc != SR_OK) return rc;
     const size_t spitch = (size_t)o.width * 4 * (size_t)ss;
     const size_t sstride = spitch * (size_t)o.nrows * (size_t)ss;
-    rc = grow(c, c->d_ss, c->ss_bytes, sstride * (size_t)o.n_frames, s);
-    if (rc != SR_OK) return rc;
     Launch sample = o;
     sample.width *= ss;
     sample.height *= ss;
@@ -703,9 +586,9 @@ int launch_ss(sr_ctx* c, const Launch& o, int ss) {
     sample.row_base *= ss;
     sample.block_rows *= ss;
     sample.block_stride *= ss;
-    rc = launch(c, sample.into(c->d_ss, spitch, o.n_frames > 1 ? sstride : 0));
+    int rc = launch_into_scratch(c, sample, sstride * (size_t)o.n_frames, spitch, o.n_frames > 1 ? sstride : 0);
     if (rc != SR_OK) return rc;
-    const hipError_t e = sr_resolve_box_device(c->d_ss, spitch, sstride, o.width, o.nrows, ss, o.d_block_list,
+    const hipError_t e = sr_resolve_box_device(c->d_ss(), spitch, sstride, o.width, o.nrows, ss, sample.d_block_list,
                                                o.block_rows, o.height, o.out, o.pitch, o.frame_stride, o.n_frames, s);
     // again at the end of the whole: a launch on another stream waits for the resolve too
     rc = finish(c, e, s);
@@ -715,7 +598,7 @@ int launch_ss(sr_ctx* c, const Launch& o, int ss) {
         c->kept.height = o.height;
         c->kept.rows = o.nrows;
         c->kept.block_rows = o.block_rows;
-        c->kept.d_blocks = o.d_block_list;
+        c->kept.d_blocks = sample.d_block_list;
     } else {
         c->kept.valid = false;
     }
@@ -757,17 +640,17 @@ int reshade(sr_ctx* c, const Launch& o) {
     const size_t spitch = (size_t)k.width * 4 * (size_t)k.ss;
     const size_t sstride = spitch * (size_t)k.rows * (size_t)k.ss;
     if (ss) {
-        rc = grow(c, c->d_ss, c->ss_bytes, sstride * (size_t)n_frames, s);
+        rc = grow(c, kSs, sstride * (size_t)n_frames, 1, s);
         if (rc != SR_OK) return rc;
         fr.out_frame_stride = (int64_t)(n_frames > 1 ? sstride : 0);
     } else {
         fr.out_frame_stride = (int64_t)o.frame_stride;
     }
-    hipError_t e = sr_launch_reshade(c->d_scene, tbl, c->d_segs, c->d_bg, c->d_arr, &fr, ss ? c->d_ss : o.out,
-                                     ss ? spitch : o.pitch, o.dbg_rgba, o.dbg_steps, c->d_ps, c->ps_n, c->d_list,
-                                     c->d_count, c->d_diag, s);
+    hipError_t e = sr_launch_reshade(c->d_scene, tbl, c->d_segs, c->d_bg, c->d_arr, &fr, ss ? c->d_ss() : o.out,
+                                     ss ? spitch : o.pitch, o.dbg_rgba, o.dbg_steps, c->d_ps(), c->ps_n(), c->d_list(),
+                                     c->d_count(), c->d_diag, s);
     if (hip_ok(e) && ss)
-        e = sr_resolve_box_device(c->d_ss, spitch, sstride, k.width, k.rows, k.ss, k.d_blocks, k.block_rows, k.height,
+        e = sr_resolve_box_device(c->d_ss(), spitch, sstride, k.width, k.rows, k.ss, k.d_blocks, k.block_rows, k.height,
                                   o.out, o.pitch, o.frame_stride, n_frames, s);
     return finish(c, e, s);
 }
@@ -885,18 +768,9 @@ void sr_destroy(sr_ctx* c) {
         release(c, c->d_bg, s);
         release(c, c->d_arr, s);
         release(c, c->d_opq, s);
-        for (auto& kv : c->tables) release(c, kv.second.dev, s);
-        for (auto& kv : c->xtabs) release(c, kv.second.dev, s);
         release(c, c->d_seq, s);
-        free_pixel_state(c, s);
-        release(c, c->d_ss, s);
-        release(c, c->d_amask, s);
-        release(c, c->d_acodes, s);
-        for (auto& kv : c->orders) {
-            release(c, kv.second.order, s);
-            release(c, kv.second.cost, s);
-        }
-        for (auto& kv : c->block_lists) release(c, kv.second.dev, s);
+        c->caches.release_all(HipDevice{c}, s);
+        for (Scratch& b : c->scratch) drop(c, b, s);
         (void)hipStreamSynchronize(s);
         (void)hipStreamDestroy(s);
     }
@@ -1008,7 +882,8 @@ int sr_set_scene_sequence(sr_ctx* c, const sr_scene* scenes, int n) {
         if (rc != SR_OK) return rc;  // the earlier sequence stays
     }
     if (!hip_ok(hipSetDevice(c->device)) || !wait_ctx(c)) return SR_E_HIP;
-    drop_xtabs(c);
+    // the tables of the sequence that goes (the frames are done, the frees stream-ordered all the same)
+    c->caches.xtabs.release_all(HipDevice{c}, c->upload);
     c->h_seq.clear();
     if (n == 0) {
         release(c, c->d_seq, c->upload);
@@ -1066,13 +941,10 @@ int sr_wave_costs(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width
 int sr_render_block_list(sr_ctx* c, const sr_camera* cams, int n_frames, const sr_params* p, int width, int height,
                          int block_rows, const int* blocks, int n_blocks, uint8_t* out, size_t pitch,
                          size_t frame_stride, sr_stream stream) {
-    int rc = check_block_list(c, out, blocks, n_blocks, block_rows, height, 1);
-    if (rc != SR_OK) return rc;
-    const int* d = nullptr;
-    rc = ensure_block_list(c, blocks, n_blocks, stream, &d);
+    const int rc = check_block_list(c, out, blocks, n_blocks, block_rows, height, 1);
     if (rc != SR_OK) return rc;
     return launch(c, Launch(cams, n_frames, p, width, height, stream)
-                         .block_list(d, n_blocks, block_rows)
+                         .block_list(blocks, n_blocks, block_rows)
                          .into(out, pitch, frame_stride));
 }
 
@@ -1085,7 +957,15 @@ int sr_render_blocks_batch(sr_ctx* c, const sr_camera* cams, int n_frames, const
                          .into(out, pitch, frame_stride));
 }
 
-static bool bad_grid(int ss);
+static bool bad_grid(int ss) { return ss < 1 || ss > SR_MAX_SUPERSAMPLE; }
+
+// The bounds of a supersampled launch's output (`rows` of it; a block list's: bounded by
+// check_block_list already): the sample frame's sizes fit an int, its rows 2^24; then the frame stride's
+static int check_ss_output(int width, int height, int rows, int ss, int n_frames, size_t pitch, size_t frame_stride) {
+    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss || rows > (1 << 24) / ss)
+        return SR_E_INVALID;
+    return n_frames > 1 && frame_stride < pitch * (size_t)rows ? SR_E_INVALID : SR_OK;
+}
 
 int sr_render_sequence(sr_ctx* c, int first_scene, const sr_camera* cams, int n_frames, const sr_params* p, int width,
                        int height, int row_begin, int row_end, int ss, uint8_t* out, size_t pitch,
@@ -1099,14 +979,8 @@ int sr_render_sequence(sr_ctx* c, int first_scene, const sr_camera* cams, int n_
                          .into(out, pitch, frame_stride);
     if (ss == 1) return launch(c, r);
     int rc = check_frames(c, cams, n_frames, p, width, height, r.seq_first);
+    if (rc == SR_OK) rc = check_ss_output(width, height, n, ss, n_frames, pitch, frame_stride);
     if (rc != SR_OK) return rc;
-    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss || n > (1 << 24) / ss)
-        return SR_E_INVALID;
-    if (n_frames > 1 && frame_stride < pitch * (size_t)n) return SR_E_INVALID;
-    if (n == 0) {  // no rows: nothing is written
-        c->kept.valid = false;
-        return SR_OK;
-    }
     return launch_ss(c, r, ss);
 }
 
@@ -1116,14 +990,10 @@ int sr_render_sequence_block_list(sr_ctx* c, int first_scene, const sr_camera* c
     if (bad_grid(ss)) return SR_E_INVALID;
     int rc = check_block_list(c, out, blocks, n_blocks, block_rows, height, ss);
     if (rc == SR_OK) rc = check_frames(c, cams, n_frames, p, width, height, first_scene < 0 ? INT32_MIN : first_scene);
-    if (rc != SR_OK) return rc;
-    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss) return SR_E_INVALID;
-    if (n_frames > 1 && frame_stride < pitch * (size_t)(n_blocks * block_rows)) return SR_E_INVALID;
-    const int* d = nullptr;
-    rc = ensure_block_list(c, blocks, n_blocks, stream, &d);
+    if (rc == SR_OK) rc = check_ss_output(width, height, n_blocks * block_rows, ss, n_frames, pitch, frame_stride);
     if (rc != SR_OK) return rc;
     const Launch r = Launch(cams, n_frames, p, width, height, stream)
-                         .block_list(d, n_blocks, block_rows)
+                         .block_list(blocks, n_blocks, block_rows)
                          .sequence(first_scene)
                          .into(out, pitch, frame_stride);
     return ss == 1 ? launch(c, r) : launch_ss(c, r, ss);
@@ -1161,22 +1031,15 @@ int sr_resolve_box(const uint8_t* samples, size_t sample_pitch, size_t sample_fr
                                         out, pitch, out_frame_stride, n_frames, reinterpret_cast<hipStream_t>(stream)));
 }
 
-static bool bad_grid(int ss) { return ss < 1 || ss > SR_MAX_SUPERSAMPLE; }
-
 int sr_render_ss(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int row_begin,
                  int row_end, int ss, uint8_t* out, size_t pitch, sr_stream stream) {
     if (bad_grid(ss)) return SR_E_INVALID;
     if (ss == 1) return sr_render(c, cam, p, width, height, row_begin, row_end, out, pitch, stream);
     if (!out || bad_rows(row_begin, row_end, height)) return SR_E_INVALID;
-    int rc = check_frames(c, cam, 1, p, width, height);
-    if (rc != SR_OK) return rc;
     const int n = row_end - row_begin;
-    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss || n > (1 << 24) / ss)
-        return SR_E_INVALID;
-    if (n == 0) {  // no rows: nothing is written
-        c->kept.valid = false;
-        return SR_OK;
-    }
+    int rc = check_frames(c, cam, 1, p, width, height);
+    if (rc == SR_OK) rc = check_ss_output(width, height, n, ss, 1, pitch, 0);
+    if (rc != SR_OK) return rc;
     return launch_ss(c, Launch(cam, 1, p, width, height, stream).band(row_begin, n).into(out, pitch), ss);
 }
 
@@ -1189,14 +1052,10 @@ int sr_render_block_list_ss(sr_ctx* c, const sr_camera* cams, int n_frames, cons
                                     frame_stride, stream);
     int rc = check_block_list(c, out, blocks, n_blocks, block_rows, height, ss);
     if (rc == SR_OK) rc = check_frames(c, cams, n_frames, p, width, height);
-    if (rc != SR_OK) return rc;
-    if (pitch < (size_t)width * 4 || width > INT32_MAX / (4 * ss) || height > INT32_MAX / ss) return SR_E_INVALID;
-    if (n_frames > 1 && frame_stride < pitch * (size_t)(n_blocks * block_rows)) return SR_E_INVALID;
-    const int* d = nullptr;
-    rc = ensure_block_list(c, blocks, n_blocks, stream, &d);
+    if (rc == SR_OK) rc = check_ss_output(width, height, n_blocks * block_rows, ss, n_frames, pitch, frame_stride);
     if (rc != SR_OK) return rc;
     return launch_ss(c, Launch(cams, n_frames, p, width, height, stream)
-                            .block_list(d, n_blocks, block_rows)
+                            .block_list(blocks, n_blocks, block_rows)
                             .into(out, pitch, frame_stride),
                      ss);
 }
@@ -1229,24 +1088,10 @@ int sr_render_accumulate(sr_ctx* c, const sr_camera* cam, const sr_params* p, in
     if (rc != SR_OK) return rc;
     if (width > INT32_MAX / 8 || accum_pitch < (size_t)width * 8 || (((uintptr_t)accum | accum_pitch) & 7) != 0)
         return SR_E_INVALID;
-    const int n = row_end - row_begin;
-    c->kept.valid = false;  // the phases' frames are not a caller's output: nothing is retained
-    if (n == 0) return SR_OK;  // no rows: nothing is written
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    rc = enter_stream(c, s);
-    if (rc != SR_OK) return rc;
-    const size_t ipitch = (size_t)width * 4, istride = ipitch * (size_t)n;
-    rc = grow(c, c->d_ss, c->ss_bytes, istride * (size_t)n_phases, s);
-    if (rc != SR_OK) return rc;
-    Launch r = Launch(cam, n_phases, p, width, height, stream).band(row_begin, n).into(c->d_ss, ipitch, istride);
+    Launch r = Launch(cam, n_phases, p, width, height, stream).band(row_begin, row_end - row_begin);
     r.grid = ss;
     r.phases = phases;
-    rc = launch(c, r);
-    c->kept.valid = false;
-    if (rc != SR_OK) return rc;
-    // again at the end of the whole: a launch on another stream waits for the add too
-    return finish(c, sr_accum_add_device(c->d_ss, ipitch, istride, n_phases, width, n, reset ? 1 : 0, accum, accum_pitch, s),
-                  s);
+    return accumulate_sub_frames(c, r, reset, accum, accum_pitch);
 }
 
 int sr_accum_add(const uint8_t* images, size_t pitch, size_t image_stride, int n_images, int width, int rows, int reset,
@@ -1346,25 +1191,19 @@ int shutter_frames(const sr_ctx* c, int first_scene, const sr_camera* cams, cons
     return SR_OK;
 }
 
-// The sub-frames into the sample scratch (rows and block list set in sl.r),
-// then their resolve to `groups` frames at `out`. No retained frame: the
-// sub-frames are not a caller's output.
+// The sub-frames (rows and block list set in sl.r), then their resolve to
+// `groups` frames at `out`
 int launch_shutter(sr_ctx* c, ShutterLaunch& sl, int sub, int groups, uint8_t* out, size_t pitch, size_t frame_stride) {
     Launch& r = sl.r;
     c->kept.valid = false;
     if (r.nrows == 0) return SR_OK;  // no rows: nothing is written
-    const hipStream_t s = reinterpret_cast<hipStream_t>(r.stream);
-    int rc = enter_stream(c, s);
-    if (rc != SR_OK) return rc;
-    const size_t ipitch = (size_t)r.width * 4, istride = ipitch * (size_t)r.nrows;
-    rc = grow(c, c->d_ss, c->ss_bytes, istride * (size_t)r.n_frames, s);
-    if (rc != SR_OK) return rc;
-    rc = launch(c, r.into(c->d_ss, ipitch, istride));
-    c->kept.valid = false;
+    const int rc = launch_sub_frames(c, r);
     if (rc != SR_OK) return rc;
     // again at the end of the whole: a launch on another stream waits for the resolve too
-    return finish(c, sr_shutter_resolve_device(c->d_ss, ipitch, istride, sub, groups, r.width, r.nrows, r.d_block_list,
-                                               r.block_rows, r.height, out, pitch, groups > 1 ? frame_stride : 0, s),
+    const hipStream_t s = reinterpret_cast<hipStream_t>(r.stream);
+    return finish(c, sr_shutter_resolve_device(c->d_ss(), r.pitch, r.frame_stride, sub, groups, r.width, r.nrows,
+                                               r.d_block_list, r.block_rows, r.height, out, pitch,
+                                               groups > 1 ? frame_stride : 0, s),
                   s);
 }
 
@@ -1398,10 +1237,7 @@ int sr_render_shutter_block_list(sr_ctx* c, int first_scene, const sr_camera* ca
     if (pitch < (size_t)width * 4 || (((uintptr_t)out | pitch) & 3) != 0) return SR_E_INVALID;
     if (n_frames > 1 && (frame_stride < pitch * (size_t)(n_blocks * block_rows) || (frame_stride & 3) != 0))
         return SR_E_INVALID;
-    const int* d = nullptr;
-    rc = ensure_block_list(c, blocks, n_blocks, stream, &d);
-    if (rc != SR_OK) return rc;
-    sl.r.block_list(d, n_blocks, block_rows);
+    sl.r.block_list(blocks, n_blocks, block_rows);
     return launch_shutter(c, sl, sub_frames, n_frames, out, pitch, frame_stride);
 }
 
@@ -1416,19 +1252,7 @@ int sr_render_accumulate_shutter(sr_ctx* c, int first_scene, const sr_camera* ca
         return SR_E_INVALID;
     const int n = row_end - row_begin;
     if (n > (1 << 24)) return SR_E_INVALID;
-    c->kept.valid = false;  // the sub-frames are not a caller's output: nothing is retained
-    if (n == 0) return SR_OK;  // no rows: nothing is written
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    rc = enter_stream(c, s);
-    if (rc != SR_OK) return rc;
-    const size_t ipitch = (size_t)width * 4, istride = ipitch * (size_t)n;
-    rc = grow(c, c->d_ss, c->ss_bytes, istride * (size_t)n_sub, s);
-    if (rc != SR_OK) return rc;
-    rc = launch(c, sl.r.band(row_begin, n).into(c->d_ss, ipitch, istride));
-    c->kept.valid = false;
-    if (rc != SR_OK) return rc;
-    // again at the end of the whole: a launch on another stream waits for the add too
-    return finish(c, sr_accum_add_device(c->d_ss, ipitch, istride, n_sub, width, n, reset ? 1 : 0, accum, accum_pitch, s), s);
+    return accumulate_sub_frames(c, sl.r.band(row_begin, n), reset, accum, accum_pitch);
 }
 
 int sr_shutter_resolve(const uint8_t* images, size_t pitch, size_t image_stride, int sub_frames, int n_frames, int width,
@@ -1494,28 +1318,29 @@ int sr_render_adaptive(sr_ctx* c, const sr_camera* cam, const sr_params* p, int 
     // nothing launched. The pixel state is the whole sample frame's (the
     // integrate kernel's ids are the frame's), which holds the plain frame's.
     const size_t spitch = (size_t)width * 4 * (size_t)ss;
-    rc = grow(c, c->d_ss, c->ss_bytes, spitch * (size_t)height * (size_t)ss, s);
-    if (rc == SR_OK) rc = grow(c, c->d_amask, c->amask_n, tiles, s);
-    if (rc == SR_OK) rc = grow(c, c->d_acodes, c->acodes_n, stiles, s);
+    rc = grow(c, kSs, spitch * (size_t)height * (size_t)ss, 1, s);
+    if (rc == SR_OK) rc = grow(c, kAmask, tiles, 1, s);
+    if (rc == SR_OK) rc = grow(c, kAcodes, stiles, sizeof(int), s);
     if (rc == SR_OK) rc = ensure_pixel_state(c, stiles * 256, s);
     if (rc != SR_OK) return rc;
     rc = launch(c, plain);  // runs and learns the plain frame's order
     c->kept.valid = false;  // the sparse sample launch below overwrites P's rays
     if (rc != SR_OK) return rc;
-    hipError_t e = sr_edge_tiles_device(out, pitch, width, height, threshold, grow_tiles, c->d_amask, s);
+    hipError_t e = sr_edge_tiles_device(out, pitch, width, height, threshold, grow_tiles, c->d_amask(), s);
     // the sample tiles in the order P's launch just learned (its shade kernel wrote it): costliest first
-    if (hip_ok(e) && (!c->last_order || c->last_slots > (size_t)INT32_MAX)) e = hipErrorInvalidValue;
+    const sr_cache::Caches& cc = c->caches;
+    if (hip_ok(e) && (!cc.last_order || cc.last_slots > (size_t)INT32_MAX)) e = hipErrorInvalidValue;
     if (hip_ok(e))
-        e = sr_adaptive_codes_device(c->d_amask, width, height, ss, c->last_order, (int)c->last_slots, c->d_acodes,
+        e = sr_adaptive_codes_device(c->d_amask(), width, height, ss, cc.last_order, (int)cc.last_slots, c->d_acodes(),
                                      dev_tile_mask, s);
     if (!hip_ok(e)) return SR_E_HIP;
     // S, the flagged tiles' part of it
-    Launch sample = Launch(cam, 1, p, ss * width, ss * height, stream).band(0, ss * height).into(c->d_ss, spitch);
-    sample.d_codes = c->d_acodes;
+    Launch sample = Launch(cam, 1, p, ss * width, ss * height, stream).band(0, ss * height).into(c->d_ss(), spitch);
+    sample.d_codes = c->d_acodes();
     rc = launch(c, sample);
     if (rc != SR_OK) return rc;
     // again at the end of the whole: a launch on another stream waits for the resolve too
-    return finish(c, sr_resolve_box_masked_device(c->d_ss, spitch, width, height, ss, c->d_amask, out, pitch, s), s);
+    return finish(c, sr_resolve_box_masked_device(c->d_ss(), spitch, width, height, ss, c->d_amask(), out, pitch, s), s);
 }
 
 int sr_render_debug(sr_ctx* c, const sr_camera* cam, const sr_params* p, int width, int height, int row_begin,
@@ -1573,7 +1398,7 @@ int sr_pick_map(sr_ctx* c, int32_t* ids, size_t pitch, size_t frame_stride, sr_s
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc = enter_stream(c, s);
     if (rc != SR_OK) return rc;
-    return finish(c, sr_launch_pick(c->d_scene, c->d_segs, &fr, c->d_ps, c->ps_n, ids, pitch,
+    return finish(c, sr_launch_pick(c->d_scene, c->d_segs, &fr, c->d_ps(), c->ps_n(), ids, pitch,
                                     fr.batch > 1 ? frame_stride : 0, s),
                   s);
 }
@@ -1602,8 +1427,8 @@ int sr_ray_maps(sr_ctx* c, const sr_ray_map_ptrs* m, size_t pitch, size_t frame_
     const float4* tbl = nullptr;  // the step table of the retained schedule, for the pixels walked on
     rc = ensure_table(c, k.max_steps, k.max_revolutions, s, &tbl);
     if (rc != SR_OK) return rc;
-    return finish(c, sr_launch_ray_maps(c->d_scene, tbl, c->d_segs, c->d_arr, &k.fr, c->d_ps, c->ps_n, m, pitch,
-                                        k.fr.batch > 1 ? frame_stride : 0, c->d_list, c->d_count, s),
+    return finish(c, sr_launch_ray_maps(c->d_scene, tbl, c->d_segs, c->d_arr, &k.fr, c->d_ps(), c->ps_n(), m, pitch,
+                                        k.fr.batch > 1 ? frame_stride : 0, c->d_list(), c->d_count(), s),
                   s);
 }
 
@@ -1656,18 +1481,7 @@ int sr_trace_rays(sr_ctx* c, const float* dev_origins, const float* dev_dirs, in
     // outward radius, where a coarse schedule's RK4 steps stop following the
     // orbit the outward lanes' exclusions assume (device_scene.h)
     if (!(fr.max_dphi <= SR_TRACE_DPHI_MAX)) fr.cull = 0;
-    if (!(c->xc_uf == fr.u_f && c->xc_dphi == fr.max_dphi)) {  // as build_frame
-        sr_pre::low_energy_exclusions(c->h_scene, fr.u_f, fr.max_dphi, c->xc_need, c->xc_peri);
-        c->xc_uf = fr.u_f;
-        c->xc_dphi = fr.max_dphi;
-    }
-    std::memcpy(fr.xlow_need, c->xc_need, sizeof fr.xlow_need);
-    std::memcpy(fr.xperi_e, c->xc_peri, sizeof fr.xperi_e);
-    fr.bg_w = c->bg_w;
-    fr.bg_h = c->bg_h;
-    fr.arr_w = c->arr_w;
-    fr.arr_h = c->arr_h;
-    fr.arr_layers = c->arr_layers;
+    context_into_frame(c, true, fr);
     fr.fast_unroll = SR_FAST_UNROLL_DEFAULT;
     fr.tiles = 1;
     fr.nrows = 1;
@@ -1789,11 +1603,12 @@ int sr_camera_rays(const sr_camera* cam, int projection, int width, int height, 
 // << 8, | 0x80 | sub for split workgroups, -1 unused). Waits for the frame.
 int sr_debug_last_order(sr_ctx* c, int* out, int max_n, int* n) {
     if (!c || !n || max_n < 0 || (max_n && !out)) return SR_E_INVALID;
-    *n = (int)c->last_slots;
-    if (!c->last_order) return SR_OK;
+    const sr_cache::Caches& cc = c->caches;
+    *n = (int)cc.last_slots;
+    if (!cc.last_order) return SR_OK;
     if (!hip_ok(hipSetDevice(c->device)) || !wait_ctx(c)) return SR_E_HIP;
-    const size_t k = c->last_slots < (size_t)max_n ? c->last_slots : (size_t)max_n;
-    if (k && (!hip_ok(hipMemcpyAsync(out, c->last_order, k * sizeof(int), hipMemcpyDeviceToHost, c->upload)) ||
+    const size_t k = cc.last_slots < (size_t)max_n ? cc.last_slots : (size_t)max_n;
+    if (k && (!hip_ok(hipMemcpyAsync(out, cc.last_order, k * sizeof(int), hipMemcpyDeviceToHost, c->upload)) ||
               !hip_ok(hipStreamSynchronize(c->upload))))
         return SR_E_HIP;
     return SR_OK;
@@ -1806,12 +1621,12 @@ int sr_debug_last_order(sr_ctx* c, int* out, int max_n, int* n) {
 // min(max_floats, n_px * SR_PS_FIELDS) floats.
 int sr_debug_pixel_state(sr_ctx* c, float* out, size_t max_floats, size_t* n_px) {
     if (!c || !n_px || (max_floats && !out)) return SR_E_INVALID;
-    *n_px = c->ps_n;
-    if (!max_floats || !c->d_ps) return SR_OK;
+    *n_px = c->ps_n();
+    if (!max_floats || !c->d_ps()) return SR_OK;
     if (!hip_ok(hipSetDevice(c->device)) || !wait_ctx(c)) return SR_E_HIP;
-    size_t k = c->ps_n * SR_PS_FIELDS;
+    size_t k = c->ps_n() * SR_PS_FIELDS;
     if (k > max_floats) k = max_floats;
-    if (!hip_ok(hipMemcpyAsync(out, c->d_ps, k * sizeof(float), hipMemcpyDeviceToHost, c->upload)) ||
+    if (!hip_ok(hipMemcpyAsync(out, c->d_ps(), k * sizeof(float), hipMemcpyDeviceToHost, c->upload)) ||
         !hip_ok(hipStreamSynchronize(c->upload)))
         return SR_E_HIP;
     return SR_OK;
