@@ -1053,6 +1053,61 @@ int sr_trace_rays(sr_ctx* ctx, const float* dev_origins, const float* dev_dirs, 
 int sr_camera_rays(const sr_camera* cam, int projection, int width, int height,
                    int row_begin, int row_end, float* origins, float* dirs);
 
+/* ---- Ray maps of ray queries (not in the reference). sr_ray_maps' lens map
+ * and G-buffer for rays the caller supplies: where on the sky a probe's ray
+ * ends, where in space an arbitrary ray first meets a surface, and with the
+ * hit point and normal the start of a second ray (a reflection, an occlusion
+ * probe, deferred shading of lens samples).
+ *
+ * Definition. The maps of ray i are what "Ray maps" gives pixel (0, 0) of the
+ * 1 x 1 frame by which "Ray queries" defines ray i: a pinhole of fov 90 with
+ * the camera at O and the axes (0, 0, V), crosshair 0, percent_black < 0, the
+ * context's current scene, test ray and texture array, and the call's params.
+ * So:
+ *   - id equals sr_trace_rays' dev_ids for the same rays and params; it is
+ *     never SR_PICK_NONE;
+ *   - end is SR_RAY_END_SKY or SR_RAY_END_OPAQUE, never SR_RAY_END_NONE:
+ *     non-finite or zero O or V are not rejected and give what the
+ *     reference's arithmetic gives;
+ *   - sky_dir and sky_uv are valid where end == SR_RAY_END_SKY: sky_dir is the
+ *     argument of that ray's get_bg call (for a flat ray normalize(+0 + V)),
+ *     sky_uv is sr_sky_uv of it. Elsewhere both hold the quiet NaN 0x7fc00000;
+ *   - the hit_* maps are valid where id >= 0; elsewhere the float maps hold the
+ *     quiet NaN and hit_step holds -1. Validity is read from id, never from a
+ *     NaN;
+ *   - hit_step is the step count the ray had executed when that surface was
+ *     found: sr_trace_rays' dev_steps where hit_base's alpha is 1, and 0 in
+ *     flat mode;
+ *   - Deferred shading: where id >= 0 and hit_base's alpha is 1, the rgb of
+ *     sr_trace_rays' float FragColor of that ray is calculate_lighting
+ *     (frag:406-437) on hit_point, hit_normal, hit_view and hit_base, and its
+ *     alpha is 1;
+ *   - params, context settings and culling are treated as sr_trace_rays treats
+ *     them: the split modes are SR_E_INVALID; crosshair, percent_black and
+ *     curved_percentage are ignored; max_steps, max_revolutions, u_f and
+ *     filter_mode are honoured, with the reference's own loop for
+ *     max_revolutions <= 0 or a negative or NaN u_f; culling is never a result;
+ *   - no background is needed: the maps look nothing up in it;
+ *   - a launch that asks for neither end nor a sky map may end each ray at its
+ *     first surface; the other maps are the same either way;
+ *   - the launch reads and writes no pixel state and uses no worklist of the
+ *     context: a retained frame stays valid across it, learned launch orders
+ *     stay untouched and sr_diag_counters keeps its meaning.
+ * A ray's maps do not depend on the other rays of the launch or on their order.
+ *
+ * Layout: dense, one entry per ray: element (ray i, component c) of a map with
+ * n components is at map[i * n + c]. Every non-NULL pointer is 4-byte aligned;
+ * only the maps whose pointer is not NULL are written, and only their n_rays
+ * entries. Inputs as sr_trace_rays'. n_rays == 0: SR_OK, nothing written.
+ * Asynchronous on `stream`, no host wait, ordered like every launch of the
+ * context. Checked before anything is launched, nothing written: SR_E_INVALID
+ * for a null context, params or maps, n_rays < 0 or above SR_TRACE_MAX_RAYS,
+ * null or misaligned inputs, all nine pointers NULL or any of them misaligned,
+ * a split mode or unknown raytrace_type or filter_mode, max_steps outside
+ * 0 .. SR_MAX_STEPS; SR_E_NOT_READY without a scene. */
+int sr_trace_ray_maps(sr_ctx* ctx, const float* dev_origins, const float* dev_dirs, int n_rays,
+                      const sr_params* params, const sr_ray_map_ptrs* maps, sr_stream stream);
+
 /* Rows a sr_render_blocks call with these arguments writes. */
 int sr_blocks_row_count(int height, int block_rows, int block_first, int block_step);
 

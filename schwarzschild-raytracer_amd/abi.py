@@ -253,6 +253,7 @@ SIGNATURES = {
     "sr_shutter_phases": (_i, [_i, _i, _p]),
     "sr_ray_maps": (_i, [_p, C.POINTER(RayMapPtrs), C.c_size_t, C.c_size_t, _p]),
     "sr_sky_uv": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "sr_trace_ray_maps": (_i, [_p, _p, _p, _i, C.POINTER(Params), C.POINTER(RayMapPtrs), _p]),
 }
 # sr_set_projection's values (sr.h "Projections")
 PROJECTION_RECTILINEAR, PROJECTION_EQUIRECT, PROJECTION_FISHEYE = 0, 1, 2
@@ -266,6 +267,7 @@ SINCE_TRACE = ("sr_trace_rays", "sr_camera_rays")
 SINCE_SHUTTER = ("sr_render_shutter", "sr_render_shutter_block_list", "sr_render_accumulate_shutter",
                  "sr_shutter_resolve", "sr_shutter_phases")
 SINCE_RAY_MAPS = ("sr_ray_maps", "sr_sky_uv")
+SINCE_TRACE_MAPS = ("sr_trace_ray_maps",)
 # sr_ray_maps' `end` codes (sr.h "Ray maps")
 RAY_END_NONE, RAY_END_SKY, RAY_END_OPAQUE = 0, 1, 2
 SHUTTER_OWN_SCENE = -1 # sr_render_shutter's first_scene for the context's own scene (sr.h "Shutter frames")
@@ -318,7 +320,8 @@ def load(path: str | os.PathLike | None = None) -> C.CDLL:
     lib = C.CDLL(str(p), mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **EXTRA_SIGNATURES}.items():
         if (name in EXTRA_SIGNATURES or name in SINCE_PROJECTIONS or name in SINCE_SEQUENCES or
-                name in SINCE_TRACE or name in SINCE_SHUTTER or name in SINCE_RAY_MAPS) and not hasattr(lib, name):
+                name in SINCE_TRACE or name in SINCE_SHUTTER or name in SINCE_RAY_MAPS or
+                name in SINCE_TRACE_MAPS) and not hasattr(lib, name):
             continue  # debug tooling and newer calls an older library (a bisection build) may lack
         fn = getattr(lib, name)
         fn.restype = res

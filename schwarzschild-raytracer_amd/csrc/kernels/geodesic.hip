@@ -4384,3 +4384,176 @@ extern "C" hipError_t sr_launch_ray_maps(const sr_dev_scene* sc, const float4* t
                        const_cast<float*>(ps), ps_n, m, pitch, frame_stride, list, count);
     return hipGetLastError();
 }
+
+// ---- ray maps of ray queries (sr.h "Ray maps of ray queries"): the lens map
+// and the first surface's G-buffer of caller-supplied rays. Emitted where
+// sr_launch_trace_maps instantiates it: after every other kernel, whose code
+// and addresses in the code object stay the parent's.
+
+// One lane per ray on sr_trace_kernel's grid. The ray's start is that
+// kernel's, restated statement for statement (not factored out: sr_trace_kernel
+// keeps its own text): nrm(+0 + V), init_pixel's radial test, build_start's
+// expressions on O, budget_init at the lane's own anchor inside integrate.
+// Then that kernel's rounds with hit_alpha in place of shade, as
+// sr_ray_maps_resume_kernel runs them: the first returned hit gives the id
+// (the step loop skips surfaces seen from behind) and, when it is an object's,
+// the first surface with the view direction and the step count of that moment;
+// a round of alpha exactly 1 ends the ray (the hole comes back as a hit of
+// SLOT_BH: alpha 1). A ray that leaves the rounds ends as sr_ray_maps_kernel's
+// flat branch and sr_ray_maps_resume_kernel end it: ST_BG in the sky along
+// r.rd, ST_FLAT by the one unbounded intersect, whose winner is the first
+// surface when nothing was hit before, unless it is seen from behind. A
+// launch of neither `end` nor a sky map leaves each ray at its first surface.
+// The lanes of a wave are unrelated rays: nothing derived from a ray is pinned
+// to an SGPR, and surface_material loads its object per lane. No pixel state,
+// no worklist.
+template <bool CULL, bool TR = false>
+__global__ __launch_bounds__(SR_WG) void sr_trace_maps_kernel(const sr_dev_scene* __restrict__ sc,
+                                                           const float4* __restrict__ tbl,
+                                                           const float* __restrict__ segs,
+                                                           const uint32_t* __restrict__ arr, sr_dev_frame fr,
+                                                           const float* __restrict__ origins,
+                                                           const float* __restrict__ dirs, int n_rays,
+                                                           sr_ray_map_ptrs m) {
+    const PS ps{nullptr, 0};
+    Tex tx;
+    tx.bg = nullptr;
+    tx.arr = arr;
+    tx.opq = nullptr;
+    const bool want_end = m.end || m.sky_dir || m.sky_uv;
+    const bool want_hit = m.hit_point || m.hit_normal || m.hit_view || m.hit_base || m.hit_step;
+    const float qn = __int_as_float(0x7fc00000);
+    for (size_t w = (size_t)blockIdx.x * SR_WG + threadIdx.x; w < (size_t)n_rays; w += (size_t)gridDim.x * SR_WG) {
+        Ray r;
+        r.ro = ld3(origins + 3 * w);
+        r.rd = nrm(F3(0.0f, 0.0f, 0.0f) + ld3(dirs + 3 * w));
+        r.nv = nrm(r.ro);
+        r.tv = F3(0.0f, 0.0f, 0.0f);
+        r.u = r.du = 0.0f;
+        r.steps = 0;
+        r.i = 0;
+        int st = -1;
+        if (fr.raytrace_type == SR_RAYTRACE_FLAT || fabsf(dot(r.rd, r.nv)) >= 1.0f - SR_EPS) {
+            st = ST_FLAT;
+        } else {  // frag:883-889
+            r.tv = nrm(cross(cross(r.nv, r.rd), r.nv));
+            r.u = 1.0f / len(r.ro);
+            r.du = -r.u * dot(r.rd, r.nv) / dot(r.rd, r.tv);
+        }
+        int code = PICK_NONE;
+        bool picked = false;
+        Hit first = no_hit();  // the first surface when it is an object's (code >= 0)
+        f3 first_view = F3(0.0f, 0.0f, 0.0f);
+        int first_step = -1;
+        int end = RAY_END_NONE;
+        HitLog log{ps, 0};  // RECORD = false: nothing is logged
+        if (st < 0) {
+            for (;;) {  // rounds: integrate to the next hit, its alpha, resume if not opaque
+                Hit hit = no_hit();
+                st = integrate<CULL, false, false, SR_MAX_BUDGET, SR_FAST_UNROLL, SR_NC_KERNEL, TR>(sc, segs, tbl, fr, tx, r,
+                                                                                                 hit, log);
+                if (st != ST_HIT) break;
+                if (!picked) {
+                    code = pick_code(hit.slot);
+                    if (code >= 0) {
+                        first = hit;
+                        first_view = -r.rd;
+                        first_step = r.steps;
+                    }
+                }
+                picked = true;
+                if (!want_end) break;
+                if (hit_alpha(sc, fr, tx, hit, -r.rd) == 1.0f) {  // frag:932
+                    end = RAY_END_OPAQUE;
+                    break;
+                }
+                r.i++;
+            }
+        }
+        if (st == ST_BG) {
+            if (!picked) code = PICK_SKY;
+            end = RAY_END_SKY;
+        } else if (st == ST_FLAT && (!picked || want_end)) {
+            // finish_ray's unbounded intersect; with no hit before it its winner is the first surface (pick_flat)
+            const Hit h = closest_hit_all(sc, segs, r.ro, r.rd, -1.0f);
+            float alpha = 0.0f;
+            bool back = false;
+            if (h.slot >= 0 && h.slot < SR_MAX_OBJECTS) {
+                SurfaceMaterial g;
+                [[clang::always_inline]] g = surface_material(sc, fr, tx, h, -r.rd, false);  // (see below)
+                back = g.back;
+                alpha = back ? 0.0f : g.base.w;
+            } else if (h.slot != SLOT_NONE) {
+                alpha = hit_alpha(sc, fr, tx, h, -r.rd);
+            }
+            if (!picked) {
+                code = h.slot == SLOT_NONE || back ? PICK_SKY : pick_code(h.slot);
+                if (code >= 0) {
+                    first = h;
+                    first_view = -r.rd;
+                    first_step = r.steps;
+                }
+            }
+            end = alpha == 1.0f ? RAY_END_OPAQUE : RAY_END_SKY;
+        }
+
+        if (m.id) m.id[w] = code;
+        if (want_end) put_ray_end(m, w, end, r.rd);
+        if (!want_hit) continue;
+        const bool valid = code >= 0;
+        f4 base = F4(qn, qn, qn, qn);
+        f3 normal = F3(qn, qn, qn);
+        if (valid && first.slot < SR_MAX_OBJECTS && (m.hit_base || m.hit_normal)) {  // the bound: memory safety
+            // inlined by force: the checked build's kernel is past the inliner's basic-block cap, and a call
+            // of a function out of line from this kernel does not compile ("illegal VGPR to SGPR copy" at
+            // pin_slot: see trace_pick_flat)
+            SurfaceMaterial g;
+            [[clang::always_inline]] g = surface_material(sc, fr, tx, first, first_view, m.hit_normal != nullptr);
+            base = g.base;
+            normal = g.normal;
+        }
+        if (m.hit_point) {
+            m.hit_point[3 * w + 0] = valid ? first.p.x : qn;
+            m.hit_point[3 * w + 1] = valid ? first.p.y : qn;
+            m.hit_point[3 * w + 2] = valid ? first.p.z : qn;
+        }
+        if (m.hit_normal) {
+            m.hit_normal[3 * w + 0] = normal.x;
+            m.hit_normal[3 * w + 1] = normal.y;
+            m.hit_normal[3 * w + 2] = normal.z;
+        }
+        if (m.hit_view) {
+            m.hit_view[3 * w + 0] = valid ? first_view.x : qn;
+            m.hit_view[3 * w + 1] = valid ? first_view.y : qn;
+            m.hit_view[3 * w + 2] = valid ? first_view.z : qn;
+        }
+        if (m.hit_base) {
+            m.hit_base[4 * w + 0] = base.x;
+            m.hit_base[4 * w + 1] = base.y;
+            m.hit_base[4 * w + 2] = base.z;
+            m.hit_base[4 * w + 3] = base.w;
+        }
+        if (m.hit_step) m.hit_step[w] = valid ? first_step : -1;
+    }
+}
+
+extern "C" hipError_t sr_launch_trace_maps(const sr_dev_scene* sc, const float4* tbl, const float* segs,
+                                           const uint32_t* arr, const sr_dev_frame* fr, const float* origins,
+                                           const float* dirs, int n_rays, const sr_ray_map_ptrs* maps,
+                                           hipStream_t stream) {
+    const bool any = maps && (maps->end || maps->id || maps->sky_dir || maps->sky_uv || maps->hit_point ||
+                              maps->hit_normal || maps->hit_view || maps->hit_base || maps->hit_step);
+    const sr_verdict v = sr_check_trace(fr, n_rays, sc && tbl && origins && dirs, any);
+    if (v != SR_LAUNCH_GO) return v == SR_LAUNCH_EMPTY ? hipSuccess : hipErrorInvalidValue;
+    const sr_trace_kind k = sr_select_trace(*fr);
+    decltype(&sr_trace_maps_kernel<true>) kernel = nullptr;
+#define SR_X(cull, tr) \
+    if (k == sr_trace_kind{cull, tr}) kernel = sr_trace_maps_kernel<cull, tr>;
+    SR_TRACE_KINDS(SR_X)
+#undef SR_X
+    if (!kernel) return hipErrorInvalidValue;
+    const unsigned groups = ((unsigned)n_rays + SR_WG - 1u) / SR_WG;
+    hipLaunchKernelGGL(kernel, dim3(groups < SR_TRACE_GROUPS ? groups : SR_TRACE_GROUPS), dim3(SR_WG), 0, stream, sc, tbl,
+                       segs, arr, *fr, origins, dirs, n_rays, *maps);
+    return hipGetLastError();
+}

@@ -49,6 +49,12 @@ hipError_t sr_launch_trace(const sr_dev_scene* sc, const float4* tbl, const floa
                            const uint32_t* arr, const sr_dev_frame* fr, const float* origins, const float* dirs,
                            int n_rays, float* out_rgba, uint8_t* out_rgba8, int32_t* out_steps, int32_t* out_ids,
                            hipStream_t stream);
+// the lens map and the first surface's G-buffer of caller-supplied rays (sr_trace_ray_maps; sr.h "Ray maps of ray
+// queries"): sr_launch_trace's rays and frame, sr_launch_ray_maps' struct of requested maps, dense (one entry per
+// ray). No pixel state and no worklist: one kernel walks each ray to its end
+hipError_t sr_launch_trace_maps(const sr_dev_scene* sc, const float4* tbl, const float* segs, const uint32_t* arr,
+                                const sr_dev_frame* fr, const float* origins, const float* dirs, int n_rays,
+                                const sr_ray_map_ptrs* maps, hipStream_t stream);
 
 // ---- assemble.hip
 hipError_t sr_assemble_blocks_device(const uint8_t* stacked, size_t rank_stride, size_t in_frame_stride,

@@ -1449,8 +1449,15 @@ int sr_sky_uv(const float dir[3], float out_uv[2]) {
 
 // ---- ray queries (sr.h): caller-supplied rays through the current scene
 
-int sr_trace_rays(sr_ctx* c, const float* dev_origins, const float* dev_dirs, int n_rays, const sr_params* p,
-                  float* dev_rgba32, uint8_t* dev_rgba8, int32_t* dev_steps, int32_t* dev_ids, sr_stream stream) {
+namespace {
+// What sr_trace_rays and sr_trace_ray_maps share: the checks of the context,
+// the rays and the params in sr.h's order, the definition's frame, and the
+// stream entered with the schedule's step table. outputs_ok: the caller's
+// check of its own output pointers (at least one, each 4-byte aligned), which
+// counts only when there are rays. *go false with SR_OK: nothing to launch.
+int trace_prepare(sr_ctx* c, const float* dev_origins, const float* dev_dirs, int n_rays, const sr_params* p,
+                  bool outputs_ok, hipStream_t s, sr_dev_frame& fr, const float4** tbl, bool* go) {
+    *go = false;
     if (!c) return SR_E_INVALID;
     if (!c->scene_set) return SR_E_NOT_READY;
     if (n_rays < 0 || n_rays > SR_TRACE_MAX_RAYS) return SR_E_INVALID;
@@ -1463,15 +1470,11 @@ int sr_trace_rays(sr_ctx* c, const float* dev_origins, const float* dev_dirs, in
     if (rc != SR_OK) return rc;
     if (p->raytrace_type != SR_RAYTRACE_CURVED && p->raytrace_type != SR_RAYTRACE_FLAT) return SR_E_INVALID;  // no uv
     if (n_rays == 0) return SR_OK;
-    const auto misaligned = [](const void* q) { return ((uintptr_t)q & 3) != 0; };
-    if (!dev_origins || !dev_dirs || misaligned(dev_origins) || misaligned(dev_dirs)) return SR_E_INVALID;
-    if (!dev_rgba32 && !dev_rgba8 && !dev_steps && !dev_ids) return SR_E_INVALID;
-    if (misaligned(dev_rgba32) || misaligned(dev_rgba8) || misaligned(dev_steps) || misaligned(dev_ids))
-        return SR_E_INVALID;
+    if (!dev_origins || !dev_dirs || (((uintptr_t)dev_origins | (uintptr_t)dev_dirs) & 3) != 0) return SR_E_INVALID;
+    if (!outputs_ok) return SR_E_INVALID;
     sr_params pp = *p;
     pp.crosshair = 0;
     pp.percent_black = -1.0f;
-    sr_dev_frame fr;
     sr_pre::derive_frame({&cam, 1, &pp, 1, 1, 1, nullptr, c->cull, SR_PROJECTION_RECTILINEAR}, c->h_scene, fr);
     // the one launch constant whose premise is the camera position ("chord
     // origins within r = 100"): the host cannot see the origins
@@ -1487,14 +1490,50 @@ int sr_trace_rays(sr_ctx* c, const float* dev_origins, const float* dev_dirs, in
     fr.nrows = 1;
     fr.block_rows = 1;
     // no pixel state, no launch order, no retained frame: the context's stay as they are
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     rc = enter_stream(c, s);
     if (rc != SR_OK) return rc;
-    const float4* tbl = nullptr;
-    rc = ensure_table(c, p->max_steps, p->max_revolutions, s, &tbl);
+    rc = ensure_table(c, p->max_steps, p->max_revolutions, s, tbl);
     if (rc != SR_OK) return rc;
+    *go = true;
+    return SR_OK;
+}
+}  // namespace
+
+int sr_trace_rays(sr_ctx* c, const float* dev_origins, const float* dev_dirs, int n_rays, const sr_params* p,
+                  float* dev_rgba32, uint8_t* dev_rgba8, int32_t* dev_steps, int32_t* dev_ids, sr_stream stream) {
+    const auto misaligned = [](const void* q) { return ((uintptr_t)q & 3) != 0; };
+    const bool outputs_ok = (dev_rgba32 || dev_rgba8 || dev_steps || dev_ids) && !misaligned(dev_rgba32) &&
+                            !misaligned(dev_rgba8) && !misaligned(dev_steps) && !misaligned(dev_ids);
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    sr_dev_frame fr;
+    const float4* tbl = nullptr;
+    bool go = false;
+    const int rc = trace_prepare(c, dev_origins, dev_dirs, n_rays, p, outputs_ok, s, fr, &tbl, &go);
+    if (!go) return rc;
     return finish(c, sr_launch_trace(c->d_scene, tbl, c->d_segs, c->d_bg, c->d_arr, &fr, dev_origins, dev_dirs, n_rays,
                                      dev_rgba32, dev_rgba8, dev_steps, dev_ids, s),
+                  s);
+}
+
+// ---- ray maps of ray queries (sr.h): sr_ray_maps' maps of sr_trace_rays' rays
+
+int sr_trace_ray_maps(sr_ctx* c, const float* dev_origins, const float* dev_dirs, int n_rays, const sr_params* p,
+                      const sr_ray_map_ptrs* m, sr_stream stream) {
+    if (!c || !p || !m) return SR_E_INVALID;
+    const void* const ptrs[9] = {m->end,        m->id,       m->sky_dir,  m->sky_uv,  m->hit_point,
+                                 m->hit_normal, m->hit_view, m->hit_base, m->hit_step};
+    bool any = false, aligned = true;
+    for (const void* q : ptrs) {
+        aligned = aligned && ((uintptr_t)q & 3) == 0;
+        any = any || q != nullptr;
+    }
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    sr_dev_frame fr;
+    const float4* tbl = nullptr;
+    bool go = false;
+    const int rc = trace_prepare(c, dev_origins, dev_dirs, n_rays, p, any && aligned, s, fr, &tbl, &go);
+    if (!go) return rc;
+    return finish(c, sr_launch_trace_maps(c->d_scene, tbl, c->d_segs, c->d_arr, &fr, dev_origins, dev_dirs, n_rays, m, s),
                   s);
 }
 

@@ -683,6 +683,41 @@ class Renderer:
         )
         return out
 
+    # ---- ray maps of ray queries (sr.h): the maps of caller-supplied rays ----
+    def trace_ray_maps(self, origins, dirs, params: abi.Params, which=tuple(abi.RAY_MAPS), out=None, stream=None):
+        """sr_trace_ray_maps: the maps named in `which` (keys of abi.RAY_MAPS)
+        of trace_rays' rays -> a dict of [N, n] tensors, one row per ray
+        (int32 for "end", "id" and "hit_step", float32 otherwise). out: a dict
+        of such tensors to write into instead. Asynchronous."""
+        t = self.torch
+        for a in (origins, dirs):
+            assert a.dtype == t.float32 and a.dim() == 2 and a.shape[1] == 3 and a.is_contiguous()
+            assert a.device == self.tdev
+        n = int(origins.shape[0])
+        assert int(dirs.shape[0]) == n
+        which = tuple(which)
+        if not which or any(k not in abi.RAY_MAPS for k in which):
+            raise ValueError(f"trace_ray_maps: maps are {tuple(abi.RAY_MAPS)}, at least one")
+        maps, ptrs = {}, abi.RayMapPtrs()
+        for key in which:
+            c, dtype = abi.RAY_MAPS[key]
+            dt = getattr(t, dtype)
+            if out is not None and key in out:
+                m = out[key]
+                assert m.is_contiguous() and m.dtype == dt and m.numel() >= n * c and m.device == self.tdev
+            else:
+                m = t.empty((n, c), dtype=dt, device=self.tdev)
+            maps[key] = m
+            if n:
+                setattr(ptrs, key, m.data_ptr())
+        abi.check(
+            self.lib.sr_trace_ray_maps(self.ctx, C.c_void_p(origins.data_ptr()) if n else None,
+                                       C.c_void_p(dirs.data_ptr()) if n else None, n, C.byref(params), C.byref(ptrs),
+                                       self._stream(stream)),
+            "sr_trace_ray_maps",
+        )
+        return maps
+
     def close(self) -> None:
         if self.ctx:
             self.lib.sr_destroy(self.ctx)

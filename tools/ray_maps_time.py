@@ -35,6 +35,44 @@ def median(v):
     return s[len(s) // 2]
 
 
+def stacked_scene(abi, sc, n_translucent=4, gap=0.5):
+    """Four translucent layers and an opaque one behind them across the camera's view (the suite's
+    stacked-layer cell): every ray logs four translucent hits and is walked on by the resume path."""
+    import ctypes as C
+
+    s = abi.Scene()
+    abi.load().sr_scene_clear(C.byref(s))
+    for m, col in ((0, (0.02, 0.04, 0.06, 0.3)), (1, (0.9, 0.2, 0.2, 1.0))):
+        M = s.materials[m]
+        for k in range(4):
+            M.color[k] = col[k]
+        M.ambient, M.diffuse, M.specular, M.shininess = 0.2, 0.8, 0.3, 16.0
+        M.texture_index, M.normal_map_index, M.double_sided_normals = -1, -1, 1
+    axes = sc._axes_from((0.0, 0.0, 1.0))  # normal +z
+    for k in range(n_translucent + 1):  # three disks, then rectangles (three of each primitive at most)
+        z = 10.0 - gap * k
+        if k < 3:
+            t, kind, idx, pos = s.disks[k].plane.transform, abi.OBJECT_DISK, k, (0.0, 2.0, z)
+            s.disks[k].radius = 12.0
+        else:
+            t, kind, idx, pos = s.rectangles[k - 3].plane.transform, abi.OBJECT_RECTANGLE, k - 3, (-8.0, 10.0, z)
+            s.rectangles[k - 3].width = s.rectangles[k - 3].height = 16.0
+        for i in range(3):
+            t.pos[i] = pos[i]
+        for i in range(9):
+            t.axes[i] = axes[i]
+        o = s.objects[k]
+        o.type, o.index, o.material_index = kind, idx, int(k == n_translucent)
+    s.num_objects = n_translucent + 1
+    s.num_lights = 1
+    L = s.lights[0]
+    for i in range(3):
+        L.transform.pos[i] = (0.0, 5.0, 14.0)[i]
+        L.color[i] = 1.0
+    L.intensity, L.attenuation_constant, L.attenuation_linear, L.attenuation_quadratic = 5.0, 1.0, 0.09, 0.032
+    return s
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -63,45 +101,8 @@ def main():
         arr, _, _ = sc.default_texture_array()
     params = abi.default_params(max_steps=args.steps, percent_black=-1.0)
 
-    def stacked(n_translucent=4, gap=0.5):
-        """Four translucent layers and an opaque one behind them across the camera's view (the suite's
-        stacked-layer cell): every ray logs four translucent hits and is walked on by the resume path."""
-        import ctypes as C
-
-        s = abi.Scene()
-        abi.load().sr_scene_clear(C.byref(s))
-        for m, col in ((0, (0.02, 0.04, 0.06, 0.3)), (1, (0.9, 0.2, 0.2, 1.0))):
-            M = s.materials[m]
-            for k in range(4):
-                M.color[k] = col[k]
-            M.ambient, M.diffuse, M.specular, M.shininess = 0.2, 0.8, 0.3, 16.0
-            M.texture_index, M.normal_map_index, M.double_sided_normals = -1, -1, 1
-        axes = sc._axes_from((0.0, 0.0, 1.0))  # normal +z
-        for k in range(n_translucent + 1):  # three disks, then rectangles (three of each primitive at most)
-            z = 10.0 - gap * k
-            if k < 3:
-                t, kind, idx, pos = s.disks[k].plane.transform, abi.OBJECT_DISK, k, (0.0, 2.0, z)
-                s.disks[k].radius = 12.0
-            else:
-                t, kind, idx, pos = s.rectangles[k - 3].plane.transform, abi.OBJECT_RECTANGLE, k - 3, (-8.0, 10.0, z)
-                s.rectangles[k - 3].width = s.rectangles[k - 3].height = 16.0
-            for i in range(3):
-                t.pos[i] = pos[i]
-            for i in range(9):
-                t.axes[i] = axes[i]
-            o = s.objects[k]
-            o.type, o.index, o.material_index = kind, idx, int(k == n_translucent)
-        s.num_objects = n_translucent + 1
-        s.num_lights = 1
-        L = s.lights[0]
-        for i in range(3):
-            L.transform.pos[i] = (0.0, 5.0, 14.0)[i]
-            L.color[i] = 1.0
-        L.intensity, L.attenuation_constant, L.attenuation_linear, L.attenuation_quadratic = 5.0, 1.0, 0.09, 0.032
-        return s
-
     scenes = {"default": (lambda: sc.scene_default(textured=True), abi.default_camera()),
-              "stacked": (stacked, sc.camera_look((0.0, 2.0, 15.0), (0.0, -2.0, -15.0)))}
+              "stacked": (lambda: stacked_scene(abi, sc), sc.camera_look((0.0, 2.0, 15.0), (0.0, -2.0, -15.0)))}
     r = pkg.Renderer(0)
     r.set_background(bg)
     r.set_texture_array(arr)
