@@ -125,6 +125,14 @@ class Renderer:
             stream = self.torch.cuda.current_stream(self.tdev)
         return C.c_void_p(stream.cuda_stream)
 
+    def _filled(self, shape, value, dtype, stream):
+        """A tensor filled on the launch's own stream: a fill on the current
+        stream is not ordered before a launch on another one."""
+        if stream is None:
+            return self.torch.full(shape, value, dtype=dtype, device=self.tdev)
+        with self.torch.cuda.stream(stream):
+            return self.torch.full(shape, value, dtype=dtype, device=self.tdev)
+
     def render(self, cam: abi.Camera, params: abi.Params, width: int, height: int, row_begin: int = 0,
                row_end: int | None = None, out=None, stream=None):
         """RGBA8 rows [row_begin, row_end) (GL order, row 0 = bottom) into a
@@ -181,7 +189,7 @@ class Renderer:
     def wave_costs(self, cam: abi.Camera, params: abi.Params, width: int, height: int, stream=None):
         """sr_wave_costs: int32 [ceil(H / 8), ceil(W / 8), 2] per 8x8 wave tile of
         the frame: {longest ray's steps, budget events}. Asynchronous."""
-        out = self.torch.zeros(((height + 7) // 8, (width + 7) // 8, 2), dtype=self.torch.int32, device=self.tdev)
+        out = self._filled(((height + 7) // 8, (width + 7) // 8, 2), 0, self.torch.int32, stream)
         abi.check(self.lib.sr_wave_costs(self.ctx, C.byref(cam), C.byref(params), width, height,
                                          C.c_void_p(out.data_ptr()), self._stream(stream)), "sr_wave_costs")
         return out
@@ -603,7 +611,7 @@ class Renderer:
         w, rows, frames, ss = self._retained_shape("sr_pick_map")
         if out is None:
             shape = (rows, w) if frames == 1 else (frames, rows, w)
-            out = self.torch.full(shape, abi.PICK_NONE, dtype=self.torch.int32, device=self.tdev)
+            out = self._filled(shape, abi.PICK_NONE, self.torch.int32, stream)
         assert out.is_contiguous() and out.dtype == self.torch.int32 and out.numel() >= frames * rows * w
         abi.check(self.lib.sr_pick_map(self.ctx, C.c_void_p(out.data_ptr()), w * 4, rows * w * 4, self._stream(stream)),
                   "sr_pick_map")
@@ -640,7 +648,7 @@ class Renderer:
                 assert m.is_contiguous() and m.dtype == dt and m.numel() >= frames * rows * w * n
             else:
                 shape = (rows, w, n) if frames == 1 else (frames, rows, w, n)
-                m = t.full(shape, fill.get(key, float("nan")), dtype=dt, device=self.tdev)
+                m = self._filled(shape, fill.get(key, float("nan")), dt, stream)
             maps[key] = m
             setattr(ptrs, key, m.data_ptr())
         abi.check(self.lib.sr_ray_maps(self.ctx, C.byref(ptrs), w, rows * w, self._stream(stream)), "sr_ray_maps")
